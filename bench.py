@@ -14,6 +14,14 @@ Multi-GPU (torchrun, one process per GPU), no data-path collective (evolutions a
       rank r of N takes the detunings j = r (mod N) of linspace(0, 150 kHz, 64) -- 64/N points each;
   --scaling weak: rank r takes j = r (mod N) of linspace(0, 150 kHz, 64 N) -- 64 points per rank.
 
+A plain run (no --full) sets up, warms up, times the --steps steps, writes --dump-outputs if given
+and prints the line: the contract's fields, `config` and `roofline` (both from the timed steps' own
+counters and HIP events, no run of their own).  Every other leg below runs only with --full, where
+the --no-* options still drop single legs.
+  --dump-outputs DIR  after the timed steps: DIR/observables.npy, what the last timed step returned
+                 to its caller (float64 [evolution, 7 observables, 101 output times]; with N > 1 ranks
+                 observables_rank<r>.npy each); the inputs are the same from run to run
+
 Extra fields of the JSON line:
   roofline       the dominant kernel (k_interval, HIP events around every launch on its own
                  stream inside the timed region) priced as SURVEY.md §8(d) prices a fused
@@ -72,11 +80,16 @@ STEPS_T = 101
 DELTA_MAX = 150_000.0
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the timed sweep (CPU baseline, 30 s grid, strong-split "
+                    "predictions, config 2, reference default, config 5; N > 1: the partitioned register)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the observables the last timed step returned to DIR/observables.npy")
     ap.add_argument("--tile-bits", type=int, default=int(os.environ.get("DSE_TILE_BITS", "13")))
     ap.add_argument("--streams", type=int, default=int(os.environ.get("DSE_STREAMS", "4")))
     ap.add_argument("--cpu-fraction", type=float, default=float(os.environ.get("DSE_CPU_FRACTION", "0.25")),
@@ -116,7 +129,7 @@ def parse():
                     "stdout JSON line is its compact summary")
     ap.add_argument("--cpu-cores", type=int, default=int(os.environ.get("DSE_CPU_CORES", "0")),
                     help="worker processes of the all-core CPU leg (0: this process's CPU share)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 # rocprofv3 FETCH_SIZE / WRITE_SIZE passes over this bench command (tools/gpu.sh traffic +
@@ -768,6 +781,23 @@ def note(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, obs: np.ndarray, rank: int = 0, world: int = 1) -> str:
+    """--dump-outputs: the observables of the last timed step as float64 [evolution, 7, n_t] in
+    path/observables.npy (observables_rank<r>.npy with several ranks).  Above DUMP_MAX_BYTES (per
+    rank: its share of them) a fixed, seeded sample of the evolutions, in their order, is kept."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(obs, dtype=np.float64)
+    keep = max(1, (DUMP_MAX_BYTES // world) // max(a[0].nbytes, 1)) if len(a) else 0
+    if len(a) > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    name = os.path.join(path, "observables.npy" if world == 1 else f"observables_rank{rank}.npy")
+    np.save(name, a)
+    return name
+
+
 def partitioned_leg(rank: int, world: int, local: int, dist, timeout: float, cmd=None) -> dict:
     """Config 5 across the job's ranks: every rank starts tools/bench_partitioned.py as a child
     process (its own gloo bootstrap on a fresh port, libdse's RCCL communicator for the data path)
@@ -812,15 +842,15 @@ def partitioned_leg(rank: int, world: int, local: int, dist, timeout: float, cmd
     return {"error": f"child rc={rc}", "child_wall_s": wall, "stderr_tail": err[-1500:]}
 
 
-def main():
+def main(argv=None):
     global HEARTBEAT
-    args = parse()
+    args = parse(argv)
     HEARTBEAT = Heartbeat()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:  # before any GPU work: the CPU leg forks worker processes
             phase("cpu_baseline")
             cpu = cpu_baseline(args.cpu_fraction, args.cpu_cores)
@@ -868,15 +898,19 @@ def main():
 
     stats = []
     warm = [args.warmup]
+    last_obs = [None]
 
     def step():
-        _, st = eng.evolve(t)
+        last_obs[0], st = eng.evolve(t)
         if warm[0] > 0:
             warm[0] -= 1
         else:
             stats.append(st)
     phase("sweep (timed steps)")
     dt = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dist)
+    if args.dump_outputs:
+        note(f"rank {rank}: outputs of the last timed step -> "
+             f"{dump_outputs(args.dump_outputs, last_obs[0], rank, world)}")
 
     if world > 1:
         note(f"rank {rank}: timed steps done ({dt:.3f} s)")
@@ -997,7 +1031,7 @@ def main():
         },
         "roofline": roof,
     }
-    if not args.no_full:
+    if args.full and not args.no_full:
         phase("full_sweep (30 s grid)")
         try:
             line["full_sweep"] = full_sweep(eng, probs, len(my_det) * world if args.scaling == "weak" else args.n_det,
@@ -1006,32 +1040,32 @@ def main():
             line["full_sweep"] = {"error": repr(exc)}
     if cpu is not None:
         line["cpu_baseline"] = cpu
-    if rank == 0 and world == 1 and not args.no_shard8:
+    if args.full and rank == 0 and world == 1 and not args.no_shard8:
         try:
             phase("strong split predictions (2/4/8 GPUs)")
             line["strong_split"] = strong_split_legs(eng, args.n_sea, args.n_det)
         except Exception as exc:  # report, never hide
             line["strong_split"] = {"error": repr(exc)}
     eng.close()
-    if rank == 0 and world == 1 and not args.no_config2:
+    if args.full and rank == 0 and world == 1 and not args.no_config2:
         try:
             phase("config2")
             line["config2"] = config2_leg(local)
         except Exception as exc:  # report, never hide
             line["config2"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not args.no_refdefault:
+    if args.full and rank == 0 and world == 1 and not args.no_refdefault:
         try:
             phase("reference_default")
             line["reference_default"] = reference_default_leg(local)
         except Exception as exc:  # report, never hide
             line["reference_default"] = {"error": repr(exc)}
-    if rank == 0 and world == 1 and not args.no_large:
+    if args.full and rank == 0 and world == 1 and not args.no_large:
         try:
             phase("large_register")
             line["large_register"] = large_register(local)
         except Exception as exc:  # report, never hide
             line["large_register"] = {"error": repr(exc)}
-    if world in (2, 4, 8) and not args.no_large:
+    if args.full and world in (2, 4, 8) and not args.no_large:
         try:
             rep = partitioned_leg(rank, world, int(os.environ.get("LOCAL_RANK", "0")), dist,
                                   args.partitioned_timeout)

@@ -45,6 +45,30 @@ def test_compact_line_is_small_and_carries_the_contract():
     assert c["detail"] == "gpurun_out/bench_detail.json"
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse(["--full", "--no-large", "--dump-outputs", "d"])
+    assert a.full and a.no_large and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float64_and_samples_large_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    obs = np.random.default_rng(1).standard_normal((12, 7, 11))
+    path = bench.dump_outputs(str(tmp_path / "a"), obs)
+    assert os.path.basename(path) == "observables.npy"
+    got = np.load(path)
+    assert got.dtype == np.float64 and np.array_equal(got, obs)
+    assert os.path.basename(bench.dump_outputs(str(tmp_path / "a"), obs, 1, 2)) == "observables_rank1.npy"
+    # above the cap: the same seeded subset of whole evolutions every time, in their order
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 5 * obs[0].nbytes + 8)
+    s1 = np.load(bench.dump_outputs(str(tmp_path / "b"), obs))
+    s2 = np.load(bench.dump_outputs(str(tmp_path / "c"), obs))
+    assert s1.shape == (5, 7, 11) and np.array_equal(s1, s2)
+    rows = [next(i for i in range(12) if np.array_equal(obs[i], r)) for r in s1]
+    assert rows == sorted(set(rows))
+
+
 def test_lds_bytes_per_amp_term_matches_the_kernel_schedule():
     # 16 amplitudes per thread; per term 9 x (16 + 64 + 8) + 19 + 16 ds_read_b128 and 16 ds_write_b128
     assert bench.LDS_B_PER_AMP_TERM == 16.0 * (9 * 88 + 51) / 16.0

@@ -7,7 +7,7 @@
 # a fault, an abort or a time limit).  Outputs land in gpurun_out/r06/<tag>/.
 #   tests[:pytest-path-or-k]   pytest -m gpu (whole suite, a file, or "-k expr" as k=expr)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:args]               python bench.py <args>  (args: comma-separated)
+#   bench[:args]               python bench.py <args>  (args: comma-separated; --full for every leg)
 #   trace                      rocprofv3 --kernel-trace --stats of the bench's sweep leg
 #   traffic                    FETCH_SIZE and WRITE_SIZE passes of the same (one counter per run)
 #   traffic_large              the same over tools/bench_large.py (N = 30, Walsh-Hadamard engine)
