@@ -179,17 +179,24 @@ const char* dse_last_error(const dse_ctx* ctx);
  *                         acquire after every poll
  *          "wht_persist"  Walsh-Hadamard engine: bit 1 runs MID as a persistent launch (one
  *                         workgroup per CU looping over tiles, next tile's loads under the other
- *                         vector's transposes); 0 (default)
+ *                         vector's transposes); 0 (default).  The half-LDS MID ("wht_half" bit 2,
+ *                         on by default) takes precedence: bit 1 here has an effect only with
+ *                         "wht_half" bit 2 cleared
  *          "wht_fuse"     Walsh-Hadamard engine, unpartitioned registers: 1 (default) the FINAL pass
  *                         of term k also runs term k + 1's FIRST on the new vector while it is in
  *                         registers (one read of it and one launch less per term; the group-0
  *                         butterflies in another order: results agree to rounding); 0 separate
+ *                         passes.  Decided once per lane group for a whole evolve: a group that
+ *                         contains any partitioned register runs unfused on every term, its
+ *                         unpartitioned registers included
  *          "wht_mid_inpage"  Walsh-Hadamard plan: the MID group's high bits below the 2-MiB page
  *                         (0 default; measured slower, kept for experiments)
  *          "wht_half"     Walsh-Hadamard engine, 13-bit tiles: passes with one vector in registers
  *                         and the LDS transposes in halves (real, then imaginary parts), two
  *                         workgroups per CU: bit 0 FIRST, bit 1 FWD / INV, bit 2 MID (default 7;
- *                         0 the one-workgroup-per-CU passes); results bitwise identical
+ *                         0 the one-workgroup-per-CU passes); results bitwise identical.  Bit 2
+ *                         takes precedence over "wht_persist" bit 1: while it is set, MID is never
+ *                         the persistent launch
  *          "dense"        dense eigen-propagator: 0 off, 1 by cost model (default), 2 always
  *          "eig_streams"  dense engine: eigendecompositions of registers of >= 2^10 amplitudes
  *                         run this many at a time, one stream and rocBLAS handle each, 1..8

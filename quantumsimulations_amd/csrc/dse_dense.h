@@ -40,7 +40,9 @@ struct DenseProb {
   double* V;            // [dim * dim] column-major: H' in, eigenvectors out (rocSOLVER)
   double* lam;          // [dim] eigenvalues (ascending); after k_dense_rq the high part of each
                         // refined eigenvalue (double-double lam + lam_lo)
-  double* lam_lo;       // [dim] low parts (zero without the refinement)
+  double* lam_lo;       // [dim] low parts; written by k_dense_rq only: without the refinement the
+                        // buffer is uninitialised and nothing may read it (k_dense_phase takes its
+                        // fp64 branch, nufft_outputs gets a null pointer)
   double* diag_dd;      // [2 dim] the exact diagonal <x|H'|x> as double-double (hi, lo), for k_dense_rq
   double* obs;          // [n_t][8] raw observable sums of this problem (finish_obs order)
   double2* final_state; // [dim] psi(t_last) in the reference frame (dse_get_state), or null
@@ -101,7 +103,8 @@ struct NufftScratch {  // device buffers of one dense_run (sized for its largest
 struct NufftCache;  // rocFFT plans (per context)
 void nufft_release(NufftCache* c);
 size_t nufft_scratch_doubles(const NufftGrid& g, int dim);
-// psi' of every output of one register (V column-major dim x dim, refined eigenvalues, psi0 = e_x0)
+// psi' of every output of one register (V column-major dim x dim, eigenvalues lam_hi + lam_lo,
+// psi0 = e_x0; lam_lo null: the unrefined eigenvalues, low parts zero, no device read of them)
 // into Psi in blocks of TB interleaved complex columns, per_block(tb0, tb) called after each block
 // (the observables, the final state); 0 on success
 int nufft_outputs(NufftCache*& cache, hipStream_t st, const NufftGrid& g, const NufftScratch& S, const double* V,

@@ -204,6 +204,7 @@ bool nufft_grid(const double* tau, int n_t, double lam_max, NufftGrid& g) {
 
 // ---- spreading tables of one register -------------------------------------------------------
 
+// lam_lo: low parts of the eigenvalues, or null (all zero: the unrefined eigenvalues)
 void nufft_sources(const NufftGrid& g, int dim, const double* lam_hi, const double* lam_lo, const double* c,
                    std::vector<int>& off, std::vector<int>& src, std::vector<double>& wt) {
   const int M = g.M;
@@ -223,7 +224,7 @@ void nufft_sources(const NufftGrid& g, int dim, const double* lam_hi, const doub
   std::vector<int> cnt(M + 1, 0);
   std::vector<double> th(dim), dre(dim), dim_(dim);
   for (int a = 0; a < dim; ++a) {
-    const hdd lam = {lam_hi[a], lam_lo[a]};
+    const hdd lam = {lam_hi[a], lam_lo ? lam_lo[a] : 0.0};
     const hdd theta = dd_mod2pi(dd_mul(lam, hdd{g.s, 0.0}));
     const hdd phase = dd_mod2pi(dd_mul(lam, hs));  // (T/2) lambda s mod 2 pi: the centring factor
     th[a] = theta.hi + theta.lo;  // position for the window search only
@@ -240,7 +241,7 @@ void nufft_sources(const NufftGrid& g, int dim, const double* lam_hi, const doub
   wt.assign(4 * (size_t)nnz, 0.0);
   std::vector<int> fill(off.begin(), off.end() - 1);
   for (int a = 0; a < dim; ++a) {
-    const hdd lam = {lam_hi[a], lam_lo[a]};
+    const hdd lam = {lam_hi[a], lam_lo ? lam_lo[a] : 0.0};
     const hdd theta = dd_mod2pi(dd_mul(lam, hdd{g.s, 0.0}));
     const int mlo = (int)std::ceil((th[a] - g.alpha) / g.h), mhi = (int)std::floor((th[a] + g.alpha) / g.h);
     for (int m = mlo; m <= mhi; ++m) {
@@ -328,17 +329,18 @@ size_t nufft_scratch_doubles(const NufftGrid& g, int dim) {
 int nufft_outputs(NufftCache*& cache, hipStream_t st, const NufftGrid& g, const NufftScratch& S, const double* V,
                   const double* lam_hi, const double* lam_lo, uint64_t x0, int dim, double* Psi, int TB,
                   const std::function<int(int tb0, int tb)>& per_block) {
-  // eigenvalues (refined) and c = row x0 of V to the host
+  // eigenvalues (refined: lam_hi + lam_lo; lam_lo null without the refinement, low parts zero and
+  // nothing read) and c = row x0 of V to the host
   hipLaunchKernelGGL(k_nufft_row, dim3((dim + 255) / 256), dim3(256), 0, st, V, dim, x0, S.c);
-  std::vector<double> lh(dim), ll(dim), c(dim);
+  std::vector<double> lh(dim), ll(lam_lo ? dim : 0), c(dim);
   if (hipMemcpyAsync(lh.data(), lam_hi, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(ll.data(), lam_lo, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (lam_lo && hipMemcpyAsync(ll.data(), lam_lo, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) ||
       hipMemcpyAsync(c.data(), S.c, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     return -1;
   std::vector<int> off, src;
   std::vector<double> wt;
-  nufft_sources(g, dim, lh.data(), ll.data(), c.data(), off, src, wt);
+  nufft_sources(g, dim, lh.data(), lam_lo ? ll.data() : nullptr, c.data(), off, src, wt);
   const size_t nnz = src.size();
   if (nnz > S.nnz_cap) return -4;
   if (hipMemcpyAsync(S.off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||

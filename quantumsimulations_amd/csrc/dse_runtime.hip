@@ -1103,15 +1103,17 @@ int wht_swap(dse_ctx* ctx, const std::vector<int>& regs, bool back, hipStream_t 
 
 // One WHT application (mode / term k) over items of problems with wht_groups == G, tile wl;
 // regs: first problem of every partitioned register among them (index swaps around MID).
-// segs: (items, count) launches of the same wl / G.
+// segs: (items, count) launches of the same wl / G.  fuse: FINAL of term k runs term k + 1's
+// FIRST; the caller decides it once for all terms of an evolve (a term that skips FIRST relies on
+// the previous term's FINAL_NEXT), never from the registers still active at term k.
 int wht_run(dse_ctx* ctx, int wl, int G, const std::vector<std::pair<const int2*, int>>& segs,
-            const std::vector<int>& regs, int mode, int k, int q, int set, hipStream_t st) {
+            const std::vector<int>& regs, bool fuse, int mode, int k, int q, int set, hipStream_t st) {
   int rc;
   auto part = [&](int pt, int vsel) -> int {
     for (const auto& sg : segs)
       HIPC(launch_wht_part(pt, wl, mode, G, ctx->d_wht, ctx->d_probs, sg.first, sg.second, k, q, set, vsel, st,
                            ctx->n_cu * (wl == 13 ? 1 : 2),
-                           ctx->wht_persist | ctx->wht_half << 8 | (ctx->wht_fuse && regs.empty()) << 16));
+                           ctx->wht_persist | ctx->wht_half << 8 | (int)fuse << 16));
     return DSE_OK;
   };
   if (regs.empty() || !ctx->swap_overlap) {
@@ -1726,7 +1728,7 @@ int apply_members(dse_ctx* ctx, int first, int count, hipStream_t st) {
     for (int i = 0; i < count; ++i) segs.push_back({ctx->probs[first + i].d_items, (int)ctx->probs[first + i].n_tiles});
     std::vector<int> regs;
     if (P0.shard_bits > 0) regs.push_back(first);
-    return wht_run(ctx, P0.L, P0.wht_groups, segs, regs, MODE_APPLY, 0, 0, 0, st);
+    return wht_run(ctx, P0.L, P0.wht_groups, segs, regs, false, MODE_APPLY, 0, 0, 0, st);
   }
   if (ctx->probs[first].dist && (rc = dist_exchange(ctx, 0, 0, st))) return rc;
   for (int i = 0; i < count; ++i) {
@@ -2307,9 +2309,10 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
               return -1;
             return 0;
           };
-          const int rc = nufft_outputs(ctx->nufft, st, ngrid, nscr, V + dim * dim * i, J.lam + dim * (i0 + i),
-                                       J.lam_lo + dim * (i0 + i), ctx->probs[J.list[i0 + i]].psi0, (int)dim, Psi, TB,
-                                       per_block);
+          // the low parts exist only after k_dense_rq: without the refinement none are passed (zero)
+          const double* lo = ctx->dense_refine ? J.lam_lo + dim * (i0 + i) : nullptr;
+          const int rc = nufft_outputs(ctx->nufft, st, ngrid, nscr, V + dim * dim * i, J.lam + dim * (i0 + i), lo,
+                                       ctx->probs[J.list[i0 + i]].psi0, (int)dim, Psi, TB, per_block);
           if (rc) return fail(ctx, DSE_ERR_HIP, "dense engine: non-uniform FFT outputs failed (" + std::to_string(rc) + ")");
           ctx->nufft_problems++;
         }
@@ -3757,12 +3760,16 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
           continue;
         }
         if (any_dist_step && (rc = dist_exchange(ctx, q ? 2 : 0, 1, ln.stream))) return rc;
+        // fused FINAL + FIRST for the whole evolve, or not at all: a group with any partitioned
+        // register (index swaps around MID) runs unfused, also on the terms past that register's degree
+        const bool fuse = ctx->wht_fuse && g.wht_regs.empty();
         auto step = [&](int mode, int na, int k) -> int {
           if (g.wht_groups) {
             std::vector<int> regs;
             for (const auto& rg : g.wht_regs)
               if (rg.second >= k) regs.push_back(rg.first);
-            return wht_run(ctx, g.L, g.wht_groups, {{ctx->d_items + g.off, na}}, regs, mode, k, q, set, ln.stream);
+            return wht_run(ctx, g.L, g.wht_groups, {{ctx->d_items + g.off, na}}, regs, fuse, mode, k, q, set,
+                           ln.stream);
           }
           HIPC(launch_step(g.L, mode, ctx->d_probs, ctx->d_items + g.off, na, k, q, set, ln.stream));
           return DSE_OK;

@@ -9,12 +9,17 @@ np.linspace's ulp-sized departures delta_j from j s -- instead of the 4 dim^2 T-
 * N = 12 and 13 registers (the transform's default range) on a 1 s / 4001-output grid against the
   GEMM path: every output and the final state (dse_get_state);
 * a grid that is not uniform keeps the GEMM (stats dense_nufft_problems = 0), and so does
-  dense_nufft = 0.
+  dense_nufft = 0;
+* dense_refine = 0 (no Rayleigh-quotient refinement, so no low parts of the eigenvalues exist): the
+  transform runs on the eigensolver's own eigenvalues with zero low parts -- N = 7 against the
+  exact fixture and N = 11 (the default range) against the GEMM path at the same setting, within
+  the one phase rounding by which the two differ.
 The N = 14 30 s oracle test (test_gpu_grid30_n14.py) runs the default, i.e. the transform."""
 import numpy as np
 import pytest
 
 from quantumsimulations_amd import problem as pb
+from quantumsimulations_amd.engine import spectral_bounds_native
 from quantumsimulations_amd.sweep import VARIANTS, sweep_point_params
 
 pytestmark = pytest.mark.gpu
@@ -34,6 +39,7 @@ def _run(engine, probs, t, **opts):
     finally:
         engine.set_option("dense", 1)
         engine.set_option("dense_nufft", 1)
+        engine.set_option("dense_refine", 1)
         engine.clear()
 
 
@@ -89,3 +95,77 @@ def test_non_uniform_grid_keeps_the_gemm(engine):
     assert np.array_equal(a, b)
     with pytest.raises(ValueError):
         engine.set_option("dense_nufft", 3)
+
+
+# ---- dense_refine = 0: the transform on unrefined eigenvalues ---------------------------------
+# Without the refinement k_dense_rq does not run and the eigenvalues' low parts do not exist: the
+# transform must take them as zero (a null pointer down to nufft_sources), i.e. use the exact
+# phases lam tau of the eigensolver's own fp64 eigenvalues.  The GEMM path at the same setting
+# rounds each phase lam * tau once in fp64, |dphi| <= (eps / 2) |lam| tau, so
+#   ||dpsi(tau)|| <= (eps / 2) lam_max tau   and   |d<O>| <= 2 ||O|| ||dpsi|| <= n_sea (eps / 2) lam_max tau
+# (||O|| <= n_sea / 2 for the sea sums, 1 / 2 for the rare spin), on top of the file's
+# transform-against-GEMM floor 1e-11.  lam_max bounds the eigenvalues of H' = H - shift from the
+# library's spectral bounds of H.
+#
+# Limitation: before the low parts were made null the transform read them from arena memory that
+# nothing had written -- whatever the allocator returned, often zeros -- so no GPU test is
+# guaranteed to fail on that code.  These tests pin the contract that now holds by construction.
+def _lam_max(prob):
+    lo, hi = spectral_bounds_native(prob)
+    return max(abs(lo - prob.shift), abs(hi - prob.shift))
+
+
+def _unrefined_bounds(probs, n_sea, t):
+    """(per-output bound on |d<O>|, bound on the final states) between the two unrefined paths."""
+    u = 0.5 * np.finfo(float).eps
+    lam = max(_lam_max(p) for p in probs)
+    tau = t - t[0]
+    return 1e-11 + n_sea * u * lam * tau, 1e-11 + u * lam * tau[-1]
+
+
+def _check_unrefined_against_gemm(label, nu, gm, s_nu, s_gm, probs, n_sea, t):
+    b_obs, b_state = _unrefined_bounds(probs, n_sea, t)
+    d = np.max(np.abs(nu[:, :6] - gm[:, :6]), axis=(0, 1))
+    ds = max(float(np.max(np.abs(a - b))) for a, b in zip(s_nu, s_gm))
+    print(f"{label}, dense_refine=0: non-uniform FFT vs GEMM outputs {d.max():.2e} (bound at the last output "
+          f"{b_obs[-1]:.2e}, max d / bound {np.max(d / b_obs):.3f}), final states {ds:.2e} (bound {b_state:.2e})")
+    assert np.all(d <= b_obs), (d.max(), int(np.argmax(d / b_obs)), b_obs)
+    assert ds <= b_state, (ds, b_state)
+
+
+def test_nufft_unrefined_n7_matches_exact_fixture_and_gemm(engine, golden):
+    """N = 7, three variants on the 2 ms / 201-output grid of traces_n7.npz, the transform forced
+    (dense_nufft = 2) without the refinement: every observable against the exact traces at the bound
+    test_dense_matches_exact_and_chebyshev_n7 applies to the same fixture, and against the GEMM path
+    at the same dense_refine = 0 within the derived phase-rounding bound (see above, also for why
+    this cannot be guaranteed to fail on the code that read unwritten low parts)."""
+    tr = golden("traces_n7.npz")
+    t = tr["t"]
+    probs = [pb.build_problem(sweep_point_params(6, 50000.0, v, 2e-3, 201)) for v in VARIANTS]
+    nu, st, s_nu = _run(engine, probs, t, dense=2, dense_nufft=2, dense_refine=0)
+    gm, st0, s_gm = _run(engine, probs, t, dense=2, dense_nufft=0, dense_refine=0)
+    assert st["dense_problems"] == 3 and st["dense_nufft_problems"] == 3 and st0["dense_nufft_problems"] == 0
+    worst = 0.0
+    for i, v in enumerate(VARIANTS):
+        for j, k in enumerate(OBS):
+            err = float(np.max(np.abs(nu[i, j] - tr[f"{v}_exact_{k}"])))
+            worst = max(worst, err)
+            assert err < 1e-10, (v, k, err)
+    print(f"N=7, dense_refine=0: non-uniform FFT outputs vs exact traces {worst:.2e}")
+    np.testing.assert_allclose(nu[:, 6], 1.0, rtol=0, atol=1e-12)
+    _check_unrefined_against_gemm("N=7 2 ms grid", nu, gm, s_nu, s_gm, probs, 6, t)
+
+
+def test_nufft_unrefined_default_range_matches_gemm(engine):
+    """n_sea = 10 (2^11 amplitudes: the transform's default range) on a 1 s / 4001-output grid with
+    the default dense_nufft and no refinement, against the GEMM path at the same dense_refine = 0
+    within the derived phase-rounding bound."""
+    n_sea = 10
+    t = np.linspace(0.0, 1.0, 4001)
+    probs = [pb.build_problem(sweep_point_params(n_sea, 40e3, v, 1.0, 4001)) for v in ("center_on", "shell_off")]
+    assert all(1 << p.n_qubits == 2048 for p in probs)
+    nu, st, s_nu = _run(engine, probs, t, dense=2, dense_refine=0)
+    gm, st0, s_gm = _run(engine, probs, t, dense=2, dense_nufft=0, dense_refine=0)
+    assert st["dense_nufft_problems"] == len(probs) and st0["dense_nufft_problems"] == 0
+    np.testing.assert_allclose(nu[:, 6], 1.0, rtol=0, atol=1e-12)
+    _check_unrefined_against_gemm("n_sea=10 1 s grid", nu, gm, s_nu, s_gm, probs, n_sea, t)
