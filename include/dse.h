@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define DSE_ABI_VERSION 13
+#define DSE_ABI_VERSION 14
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
 
@@ -118,7 +118,8 @@ typedef struct dse_stats {
                               /* (option "eig_spin_limit"; ABI 12)                                */
   int32_t dense_nufft_problems; /* dense registers whose output times came from the non-uniform  */
                               /* FFT instead of the GEMM (option "dense_nufft"; ABI 13)           */
-  int32_t reserved13;
+  int32_t site_obs_problems;  /* registers whose site-resolved sums this call produced (option  */
+                              /* "site_obs"; a loopback partitioned register counts once; ABI 14) */
   double dense_output_ms;     /* host wall time of the dense engine's output stage (refinement,   */
                               /* transform or GEMM, observables)                                   */
 } dse_stats;
@@ -265,7 +266,17 @@ const char* dse_last_error(const dse_ctx* ctx);
  *                         dense_nufft_problems; ABI 13)
  *          "dense_refine" dense engine: 1 (default) eigenvalues refined by double-double
  *                         Rayleigh quotients (exact diagonal) and output phases reduced modulo
- *                         2 pi in double-double; 0 the eigensolver's values and fp64 phases */
+ *                         2 pi in double-double; 0 the eigensolver's values and fp64 phases
+ *          "site_obs"     0 (default): the seven aggregates only; 1: dse_evolve also keeps, for every
+ *                         register and output time, <Ix_b>, <Iy_b>, <Iz_b> of every register bit b
+ *                         (the definitions above, of the normalised state), read back with
+ *                         dse_get_site_obs.  The aggregates are bitwise what they are with 0, and
+ *                         the option does not influence which engine a register runs on.  Costs one
+ *                         more read of the state per output (plus n - L partner-tile reads per tile)
+ *                         and a second partial arena of 3 n_max + 1 doubles per tile and output
+ *                         slot (capped at 256 MiB like the first).  Not available for a register
+ *                         partitioned over processes (shard_rank >= 0): dse_evolve returns
+ *                         DSE_ERR_ARG; any value but 0 or 1 is DSE_ERR_ARG (ABI 14) */
 int dse_set_option(dse_ctx* ctx, const char* key, double value);
 
 /* ---- problems ----------------------------------------------------------------------------- */
@@ -326,11 +337,25 @@ int dse_wht_plan(int n_local, int shard_bits, int tile_bits, int max_bits, int32
 int dse_apply_h(dse_ctx* ctx, int problem, const double* psi_in, double* psi_out);
 /* The 7 observables of an arbitrary state of one problem (same kernel as dse_evolve). */
 int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7);
+/* The site-resolved sums of an arbitrary state of one problem: out[3][n], component 0 Ix, 1 Iy,
+ * 2 Iz of register bit b, of the normalised state (the hook beside dse_observables; runs the
+ * kernel of the option "site_obs" whatever the option's value; a loopback partitioned register:
+ * shard 0's id and the whole 2^n state; not available for a dist shard, DSE_ERR_ARG). */
+int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out);
 /* Evolves every problem from its basis state psi0 at t[0] through the output times t[0..n_t)
  * (strictly increasing) with an exact Chebyshev propagator (truncation tolerance tol, e.g.
  * 1e-14) and writes obs_out[problem][DSE_N_OBS][n_t].  stats may be NULL. */
 int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_out,
                dse_stats* stats);
+/* After dse_evolve with option "site_obs" = 1: out[3][n][n_t], component 0 Ix, 1 Iy, 2 Iz of
+ * register bit b at output j, of the normalised state; n = the register's qubits (a loopback
+ * partitioned register: shard 0's id, whole register; other shard ids DSE_ERR_ARG).
+ * DSE_ERR_STATE before an evolve or with the option off, and after any dse_evolve that did not
+ * return DSE_OK (every dse_evolve call, failed ones included, ends the previous call's results). */
+int dse_get_site_obs(dse_ctx* ctx, int problem, double* out);
+/* n_t of the results dse_get_site_obs would return (the size its caller allocates from), 0 when
+ * there are none. */
+int dse_site_obs_outputs(const dse_ctx* ctx);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);
 /* Energy of the final state after dse_evolve, on the device: e_out[0] = <psi|H|psi> / <psi|psi>,

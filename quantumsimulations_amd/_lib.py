@@ -20,7 +20,7 @@ DSE_ERR_CONVERGENCE = -4
 DSE_ERR_STATE = -5
 DSE_ERR_NODEVICE = -6
 DSE_N_OBS = 7
-DSE_ABI_VERSION = 13
+DSE_ABI_VERSION = 14
 
 EXPORTED = (
     "dse_abi_version", "dse_device_count", "dse_spectral_bounds", "dse_bessel_j",
@@ -28,7 +28,8 @@ EXPORTED = (
     "dse_add_problem", "dse_num_problems", "dse_clear", "dse_apply_h", "dse_observables",
     "dse_evolve", "dse_get_state", "dse_time_step_kernel", "dse_add_problem_sharded",
     "dse_dist_unique_id", "dse_dist_init", "dse_problem_dim", "dse_wht_plan", "dse_energy",
-    "dse_device_memory", "dse_dist_init_exchange",
+    "dse_device_memory", "dse_dist_init_exchange", "dse_site_observables", "dse_get_site_obs",
+    "dse_site_obs_outputs",
 )
 DSE_DIST_ID_BYTES = 128
 DSE_XCHG_ALLTOALL, DSE_XCHG_SENDRECV, DSE_XCHG_ALLREDUCE_F64 = 1, 2, 3
@@ -72,7 +73,7 @@ class DseStats(C.Structure):
         ("real_problems", C.c_int32),
         ("eig_fallbacks", C.c_int32),
         ("dense_nufft_problems", C.c_int32),
-        ("reserved13", C.c_int32),
+        ("site_obs_problems", C.c_int32),
         ("dense_output_ms", C.c_double),
     ]
 
@@ -106,6 +107,9 @@ def _declare(lib):
         "dse_observables": (C.c_int, [_vp, C.c_int, _dp, _dp]),
         "dse_evolve": (C.c_int, [_vp, _dp, C.c_int, C.c_double, _dp, C.POINTER(DseStats)]),
         "dse_get_state": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_site_observables": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+        "dse_get_site_obs": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_site_obs_outputs": (C.c_int, [_vp]),
         "dse_energy": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_device_memory": (C.c_int, [C.c_int, _dp]),
         "dse_dist_init_exchange": (C.c_int, [_vp, C.c_int, C.c_int, EXCHANGE_FN, C.c_void_p]),

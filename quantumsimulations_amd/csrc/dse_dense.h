@@ -46,6 +46,7 @@ struct DenseProb {
   double* diag_dd;      // [2 dim] the exact diagonal <x|H'|x> as double-double (hi, lo), for k_dense_rq
   double* obs;          // [n_t][8] raw observable sums of this problem (finish_obs order)
   double2* final_state; // [dim] psi(t_last) in the reference frame (dse_get_state), or null
+  double* sites;        // option site_obs: [n_t][S] raw site sums (k_dense_obs_sites), else null
 };
 
 // H' of every problem into its (zeroed) V
@@ -67,6 +68,13 @@ hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const double
 // (d->rot = 0: the computational frame) into d->obs rows t0 .. t0 + n_states
 hipError_t launch_state_obs(const DenseProb* d, int dim, const double2* states, int n_states, int t0,
                             hipStream_t st);
+// option site_obs: the site-resolved sums of the same columns into d[p].sites rows t0 .. t0 + tb of
+// S >= site_stride(n) doubles (X_b Y_b Z_b at [3 b + c], ||psi||^2 at [3 n]); _c: one problem,
+// interleaved complex columns (launch_dense_obs_c's and launch_state_obs's layout)
+hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                  int tb, int t0, int S, hipStream_t st);
+hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                    hipStream_t st);
 // psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
 // the shift's phase exp(-i shift tau_last) included)
 hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,

@@ -269,6 +269,66 @@ k_dense_obs(const DenseProb* __restrict__ probs, int dim, const double* __restri
   }
 }
 
+// Site-resolved sums of the same columns (option site_obs; layout parameters and the rotated
+// frame's factor -i as k_dense_obs): P.sites row t0 + j holds X_b Y_b Z_b at [3 b + c] for every bit
+// b < n and ||psi||^2 at [3 n], S doubles per row.  One pass over the column per bit (the column
+// stays in L2), its three sums reduced over the wave, then the four waves in order: no atomics.
+__global__ void __launch_bounds__(256)
+k_dense_obs_sites(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ Psi, size_t pstride,
+                  size_t colstride, size_t imoff, int es, int t0, int S) {
+  __shared__ double red[4][4];
+  const DenseProb& P = probs[blockIdx.y];
+  const int j = blockIdx.x;
+  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
+  const double* im = re + imoff;
+  const int n = P.n;
+  double* o = P.sites + (size_t)(t0 + j) * S;
+  const int w = threadIdx.x >> 6;
+  for (int b = 0; b <= n; ++b) {  // b == n: the norm alone
+    double v[3] = {0, 0, 0};
+    for (uint32_t x = threadIdx.x; x < (uint32_t)dim; x += 256u) {
+      const double ar = re[(size_t)x * es], ai = im[(size_t)x * es];
+      const double p2 = ar * ar + ai * ai;
+      if (b == n) {
+        v[2] += p2;
+        continue;
+      }
+      if ((x >> b) & 1u) {
+        v[2] -= 0.5 * p2;
+        continue;
+      }
+      v[2] += 0.5 * p2;
+      const uint32_t y = x | (1u << b);
+      const double br = re[(size_t)y * es], bi = im[(size_t)y * es];
+      double zr = ar * br + ai * bi, zi = ar * bi - ai * br;  // conj(a) b
+      if (P.rot) {  // -i z
+        const double t = zr;
+        zr = zi;
+        zi = -t;
+      }
+      v[0] += zr;
+      v[1] += zi;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) red[w][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      const double t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+      if (b < n)
+        o[3 * b + threadIdx.x] = t;
+      else if (threadIdx.x == 2)
+        o[3 * n] = t;
+    }
+    __syncthreads();
+  }
+  for (int i = 3 * n + 1 + threadIdx.x; i < S; i += 256) o[i] = 0.0;
+}
+
 // column tb - 1 of Psi' (layout as k_dense_obs: colstride, imoff, es)
 __global__ void __launch_bounds__(256)
 k_dense_final(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ Psi, size_t pstride,
@@ -337,6 +397,21 @@ hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const doub
 hipError_t launch_dense_obs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, hipStream_t st) {
   hipLaunchKernelGGL(k_dense_obs, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
                      (size_t)1, 2, t0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                  int tb, int t0, int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
+                     (size_t)tb * dim, 1, t0, S);
+  return hipGetLastError();
+}
+
+// interleaved complex columns, one problem: the non-uniform FFT's blocks and matrix mode's states
+hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                    hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
+                     (size_t)1, 2, t0, S);
   return hipGetLastError();
 }
 

@@ -26,6 +26,10 @@ constexpr int kIvWaves = 8;                       // hand-off flags per tile (on
 #endif
 constexpr int kMaxOut = 2;      // output times per launch of k_interval / k_real (sums in registers)
 constexpr int kSpanMaxOut = 4;  // output times per k_span launch (staggered sums, coef_nterm)
+constexpr int kMaxQubits = 34;                    // DSE_MAX_QUBITS
+// Site-resolved observables: sums per register and state, X_b Y_b Z_b at [3 b + c] for b < n and
+// ||psi||^2 at [3 n], padded to an even count (16-byte records)
+__host__ __device__ constexpr int site_stride(int n) { return (3 * n + 2) & ~1; }
 constexpr int kMaxShardBits = 3;                  // partitioned registers: up to 8 shards
 constexpr int kMaxShards = 1 << kMaxShardBits;
 // bits above an L-bit tile for the largest register (34 qubits), at least the 32-bit tile index
@@ -272,6 +276,11 @@ hipError_t launch_basis_init(const BasisInit* list, int n_entries, uint64_t max_
 hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                       double* partial, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                       int xq = 0);  // xq: launch parity of the intermediate outputs (xacc_q set)
+// site-resolved sums of the same outputs (k_obs_sites): S >= site_stride(n) doubles per tile, output
+// j's partials at partial + j * out_stride
+hipError_t launch_obs_sites(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                            double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
+                            int xq = 0);
 // partial[2 * block + {0, 1}] = block sums of Re(conj(a) b) and |a|^2 over n amplitudes
 hipError_t launch_dot(const double2* a, const double2* b, size_t n, double* partial, int blocks,
                       hipStream_t st);

@@ -8,6 +8,7 @@
 //                            8 amplitudes per thread, fused recurrence + propagator accumulation
 //   k_step_generic<L, MODE>  the same step for tiny tiles (L < 9)
 //   k_obs<L>                 <Ix>, <Iy>, <Iz> sums (sea / rare) and ||psi||^2 per tile
+//   k_obs_sites<L>           the same sums per register bit (option site_obs), 3 n + 1 per tile
 //
 // MODE_APPLY: out = H w (test hook)      MODE_FIRST: w1 = Ht w0,  acc = a0 w0 + a1 w1
 // MODE_GEN:   w_k = 2 Ht w_{k-1} - w_{k-2} (in place over w_{k-2}),  acc += a_k w_k
@@ -302,6 +303,137 @@ k_obs(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bse
   }
 }
 
+// Site-resolved observables of one state (option site_obs, dse_site_observables): per tile the
+// S = site_stride(n_max) partial sums
+//   [3 b + 0] X_b = sum_{bit_b(x)=0} Re(conj(psi_x) psi_{x^e_b})   [3 b + 1] Y_b = Im(...)
+//   [3 b + 2] Z_b = sum |psi_x|^2 s_b(x)        for every bit b < P.n,      [3 P.n] ||psi||^2
+// (zero beyond).  Arguments, addressing and the three routes of a bit (register bit: another row
+// of this thread; thread bit: LDS partner, sign constant per lane; bit >= L: partner tile through
+// tile_ptr) are k_obs's.  No thread holds more than one bit's sums: each bit is reduced over the
+// wave as soon as it is formed and lane 0 leaves it in s_red[b][wave]; after one barrier thread i
+// adds entry i over the waves in order.  Fixed order, no atomics: bitwise reproducible.  Z_b of a
+// bit >= L is +-||psi_tile||^2 / 2, formed from the tile's norm in that last step.
+template <int L>
+__global__ void __launch_bounds__(Geo<L>::NT)
+k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bsel_last,
+            double* __restrict__ partial, size_t out_stride, int xq, int S) {
+  using G = Geo<L>;
+  constexpr int T = G::T, NT = G::NT, R = G::R, NW = NT / 64, TB = G::TB;
+  __shared__ double2 s_w[T];
+  __shared__ double s_red[kMaxQubits][NW][3];
+  __shared__ double s_n2[NW];
+
+  const int2 it = items[blockIdx.x];
+  const DevProb& P = probs[it.x];
+  const uint32_t h = (uint32_t)it.y;
+  const uint32_t hg = P.h_base | h;
+  const int tid = threadIdx.x;
+  const int wv = tid >> 6;
+  const bool lane0 = (tid & 63) == 0;
+  const bool live = (T >= NT) || (tid < T);
+  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
+  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
+  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
+  const size_t base = (size_t)h << L;
+  const int n = P.n;
+
+  double2 own[R];
+  double p2[R];
+  double p2sum = 0.0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    own[r] = make_double2(0.0, 0.0);
+    if (live) {
+      own[r] = psi[base + r * NT + tid];
+      s_w[r * NT + tid] = own[r];
+    }
+    p2[r] = own[r].x * own[r].x + own[r].y * own[r].y;
+    p2sum += p2[r];
+  }
+  __syncthreads();
+
+  // wave butterfly of one bit's three sums (every lane takes part), lane 0 stores them
+  auto wave_put = [&](int b, double x, double y, double z) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      x += __shfl_xor(x, off, 64);
+      y += __shfl_xor(y, off, 64);
+      z += __shfl_xor(z, off, 64);
+    }
+    if (lane0) {
+      s_red[b][wv][0] = x;
+      s_red[b][wv][1] = y;
+      s_red[b][wv][2] = z;
+    }
+  };
+  {
+    double v = p2sum;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane0) s_n2[wv] = v;
+  }
+#pragma unroll
+  for (int b = 0; b < L; ++b) {
+    if (b >= n) continue;  // (uniform; no early exit, so the loop unrolls around the wave shuffles)
+    double ore = 0.0, oim = 0.0, oz = 0.0;
+    if (b >= TB) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if ((r >> (b - TB)) & 1) {
+          oz -= 0.5 * p2[r];
+          continue;
+        }
+        oz += 0.5 * p2[r];
+        const double2 s = own[r ^ (1 << (b - TB))];
+        ore += own[r].x * s.x + own[r].y * s.y;
+        oim += own[r].x * s.y - own[r].y * s.x;
+      }
+    } else if ((tid >> b) & 1) {
+      oz = -0.5 * p2sum;
+    } else {
+      oz = 0.5 * p2sum;
+      if (live) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const double2 s = s_w[(uint32_t)(r * NT + tid) ^ (1u << b)];
+          ore += own[r].x * s.x + own[r].y * s.y;
+          oim += own[r].x * s.y - own[r].y * s.x;
+        }
+      }
+    }
+    wave_put(b, ore, oim, oz);
+  }
+  for (int b = L; b < n; ++b) {
+    if ((hg >> (b - L)) & 1u) continue;  // uniform: this tile holds bit value 1, no X / Y terms
+    const uint32_t hp = hg ^ (1u << (b - L));
+    // intermediate outputs (bsel >= 3) live only in this context, unsharded
+    const double2* src = bsel < 3 ? tile_ptr(P, bsel, hp)
+                                  : psi + ((size_t)(hp & ((1u << P.tbl) - 1u)) << L);
+    double ore = 0.0, oim = 0.0;
+    if (live) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const double2 s = src[r * NT + tid];
+        ore += own[r].x * s.x + own[r].y * s.y;
+        oim += own[r].x * s.y - own[r].y * s.x;
+      }
+    }
+    wave_put(b, ore, oim, 0.0);
+  }
+  __syncthreads();
+  for (int i = tid; i < S; i += NT) {
+    double v = 0.0;
+    const int b = i / 3, c = i - 3 * b;
+    if (i == 3 * n || (b < n && b >= L && c == 2)) {
+      for (int w = 0; w < NW; ++w) v += s_n2[w];
+      if (i != 3 * n) v *= ((hg >> (b - L)) & 1u) ? -0.5 : 0.5;
+    } else if (b < n && !(b >= L && ((hg >> (b - L)) & 1u))) {
+      for (int w = 0; w < NW; ++w) v += s_red[b][w][c];
+    }
+    partial[i] = v;
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------
 // register-block step kernel
@@ -490,6 +622,14 @@ hipError_t launch_obs_L(const DevProb* probs, const int2* items, int n_items, in
   return hipGetLastError();
 }
 
+template <int L>
+hipError_t launch_obs_sites_L(const DevProb* probs, const int2* items, int n_items, int bsel,
+                              double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
+  hipLaunchKernelGGL((k_obs_sites<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
+                     bsel, partial, out_stride, xq, S);
+  return hipGetLastError();
+}
+
 // <a|b> pieces for dse_energy: per block sum Re(conj(a) b) and sum |a|^2 over a grid-stride
 // range (fixed grid, fixed order: bitwise deterministic).
 __global__ void __launch_bounds__(256)
@@ -542,6 +682,19 @@ hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_item
   switch (L) {
 #define X(l) \
   case l: return launch_obs_L<l>(probs, items, n_items, bsel, partial, st, n_out, out_stride, xq);
+    DSE_TILE_CASES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_obs_sites(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                            double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
+  if (n_items <= 0 || n_out <= 0) return hipSuccess;
+  if ((n_out > 1 && bsel >= 3) || S < 2) return hipErrorInvalidValue;
+  switch (L) {
+#define X(l) \
+  case l: return launch_obs_sites_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
     DSE_TILE_CASES(X)
 #undef X
     default: return hipErrorInvalidValue;

@@ -154,6 +154,17 @@ struct dse_ctx {
   int64_t total_items = 0;
   double* d_partial = nullptr;
   size_t partial_slots = 0;
+  // site-resolved observables (option "site_obs", dse_site_observables): a second partial arena for
+  // k_obs_sites, site_S doubles per tile and slot (site_stride of the context's widest register),
+  // and the results of the last evolve, per register [3][n][n_t] (loopback group: shard 0's entry)
+  int site_obs = 0;
+  double* d_site_partial = nullptr;
+  size_t site_slots = 0;
+  int site_S = 0;
+  std::vector<std::vector<double>> site_store;
+  int site_nt = 0;                  // output times of site_store (0: none)
+  double* d_small_sites = nullptr;  // small engine: [problem][n_t][kSmallSiteStride] raw site sums
+  size_t small_sites_cap = 0;
   std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
   bool prepared = false;
   bool evolved = false;
@@ -462,6 +473,12 @@ void free_device(dse_ctx* ctx) {
   if (ctx->d_items) (void)hipFree(ctx->d_items), ctx->d_items = nullptr;
   if (ctx->d_items_iv) (void)hipFree(ctx->d_items_iv), ctx->d_items_iv = nullptr;
   if (ctx->d_partial) (void)hipFree(ctx->d_partial), ctx->d_partial = nullptr;
+  if (ctx->d_site_partial) (void)hipFree(ctx->d_site_partial), ctx->d_site_partial = nullptr;
+  ctx->site_slots = 0;
+  if (ctx->d_small_sites) (void)hipFree(ctx->d_small_sites), ctx->d_small_sites = nullptr;
+  ctx->small_sites_cap = 0;
+  ctx->site_store.clear();
+  ctx->site_nt = 0;
   for (auto& kv : ctx->zzlo_tables) (void)hipFree(kv.second);
   if (ctx->d_flags) (void)hipFree(ctx->d_flags), ctx->d_flags = nullptr;
   ctx->flags_cap = 0;
@@ -1169,6 +1186,46 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
   return DSE_OK;
 }
 
+// the second arena, for k_obs_sites: slots x total_items x S doubles, S = site_stride of the widest
+// register of the context
+int ensure_site_partial(dse_ctx* ctx, size_t slots) {
+  int n_max = 1;
+  for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
+  const int S = site_stride(n_max);
+  if (ctx->site_slots >= slots && ctx->site_S == S) return DSE_OK;
+  if (ctx->d_site_partial) (void)hipFree(ctx->d_site_partial), ctx->d_site_partial = nullptr;
+  ctx->site_slots = 0;
+  if (hipMalloc(&ctx->d_site_partial, slots * ctx->total_items * S * sizeof(double)) != hipSuccess)
+    return fail(ctx, DSE_ERR_OOM, "device allocation of site-observable partials failed");
+  ctx->site_slots = slots;
+  ctx->site_S = S;
+  return DSE_OK;
+}
+
+// raw site sums v (X_b Y_b Z_b at [3 b + c], ||psi||^2 at [3 n]) of an n-qubit register, normalised
+// into o[c][b] at o[(c * n + b) * stride]
+void finish_sites(int n, const double* v, double* o, size_t stride) {
+  const double n2 = v[3 * n];
+  const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
+  for (int b = 0; b < n; ++b)
+    for (int c = 0; c < 3; ++c) o[((size_t)c * n + b) * stride] = v[3 * b + c] * inv;
+}
+
+// A fresh store for this evolve (dse_evolve has already marked the old one invalid, site_nt = 0; it
+// becomes readable again only when the evolve succeeds).  The re-run after a hand-off timeout starts over as well (its
+// results overwrite the first pass's), except for the dense registers, whose first-pass results
+// are kept like their aggregates (dense_run is not repeated).
+void reset_site_store(dse_ctx* ctx, int n_t) {
+  ctx->site_store.resize(ctx->probs.size());
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    std::vector<double>& st = ctx->site_store[pi];
+    const size_t want = ctx->site_obs && !(P.shard_bits > 0 && P.shard_rank != 0) ? (size_t)3 * P.n * n_t : 0;
+    if (ctx->rerun && P.dn && st.size() == want) continue;
+    st.assign(want, 0.0);  // (a loopback group's sums live in shard 0's entry)
+  }
+}
+
 void finish_obs(const HostProblem& P, const double* v, double* o, size_t stride) {
   const double n2 = v[6];
   const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
@@ -1213,6 +1270,26 @@ int flush_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t, double* obs_
       } else {
         finish_obs(P, v, obs_out + pi * DSE_N_OBS * (size_t)n_t + (t0 + s), (size_t)n_t);
       }
+    }
+  }
+  if (!ctx->site_obs) return DSE_OK;
+  // the site sums of the same slots: tiles in order, a loopback group's members into shard 0's record
+  const size_t S = (size_t)ctx->site_S;
+  std::vector<double> hs(nslots * ctx->total_items * S);
+  HIPC(hipMemcpy(hs.data(), ctx->d_site_partial, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> v(S);
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    if (P.side() || ctx->site_store[pi].empty()) continue;
+    const size_t n_members = P.shard_bits > 0 ? (size_t(1) << P.shard_bits) : 1;
+    for (size_t s = 0; s < nslots; ++s) {
+      std::fill(v.begin(), v.end(), 0.0);
+      for (size_t mi = pi; mi < pi + n_members; ++mi) {
+        const double* row = hs.data() + (s * ctx->total_items + ctx->item_pos[mi]) * S;
+        for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t)
+          for (int j = 0; j <= 3 * P.n; ++j) v[j] += row[t * S + j];
+      }
+      finish_sites(P.n, v.data(), ctx->site_store[pi].data() + (t0 + s), (size_t)n_t);
     }
   }
   return DSE_OK;
@@ -1371,6 +1448,9 @@ int dse_set_option(dse_ctx* ctx, const char* key, double value) {
     ctx->n_streams = (int)value;
     ctx->evolved = false;
     return ensure_lanes(ctx);
+  } else if (k == "site_obs") {  // site-resolved observables beside the seven aggregates
+    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "site_obs must be 0 or 1");
+    ctx->site_obs = (int)value;
   } else if (k == "persistent") {
     ctx->persistent = value != 0.0;
   } else if (k == "swap_overlap") {
@@ -1873,6 +1953,17 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     ctx->small_cap = desc.size();
   }
   HIPC(hipMemcpy(ctx->d_small, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
+  if (ctx->site_obs) {
+    const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallSiteStride;
+    if (sn > ctx->small_sites_cap) {
+      if (ctx->d_small_sites) (void)hipFree(ctx->d_small_sites), ctx->d_small_sites = nullptr;
+      ctx->small_sites_cap = 0;
+      if (hipMalloc(&ctx->d_small_sites, sn * sizeof(double)) != hipSuccess)
+        return fail(ctx, DSE_ERR_OOM, "small-engine site output allocation failed");
+      ctx->small_sites_cap = sn;
+    }
+  }
+  double* const d_sites = ctx->site_obs ? ctx->d_small_sites : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
   if (outn > ctx->small_out_cap) {
     if (ctx->d_small_out) (void)hipFree(ctx->d_small_out), ctx->d_small_out = nullptr;
@@ -1894,13 +1985,13 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second,
-                           ctx->d_small_out, st));
+                           ctx->d_small_out, st, d_sites));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux + iv_off, ctx->d_small_out, st));
+                        cnt, ctx->d_small_aux + iv_off, ctx->d_small_out, st, d_sites));
       *launches += 1.0;
     }
   }
@@ -1920,6 +2011,16 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
     for (int ti = 0; ti < n_t; ++ti)
       finish_obs(P, h.data() + (pi * (size_t)n_t + ti) * 8, obs_out + pi * DSE_N_OBS * (size_t)n_t + ti,
                  (size_t)n_t);
+  }
+  if (!ctx->site_obs) return DSE_OK;
+  std::vector<double> hs(ctx->probs.size() * (size_t)n_t * kSmallSiteStride);
+  HIPC(hipMemcpy(hs.data(), ctx->d_small_sites, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    if (!P.sm) continue;
+    for (int ti = 0; ti < n_t; ++ti)
+      finish_sites(P.n, hs.data() + (pi * (size_t)n_t + ti) * kSmallSiteStride, ctx->site_store[pi].data() + ti,
+                   (size_t)n_t);
   }
   return DSE_OK;
 }
@@ -2006,6 +2107,7 @@ struct DenseJob {
   DevArena ba;
   double *V = nullptr, *lam = nullptr, *lam_lo = nullptr, *E = nullptr, *Pm = nullptr, *Psi = nullptr, *obs = nullptr;
   double* diag_dd = nullptr;
+  double* sites = nullptr;  // option site_obs: [cnt][n_t][site_stride(n)] raw site sums
   rocblas_int* info = nullptr;
   DenseProb* d_desc = nullptr;
 };
@@ -2090,7 +2192,8 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       // outputs per block: P and Psi' of a problem take 2 x dim x 2 TB doubles (<= 256 MiB each)
       const int TB = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_t, (size_t(256) << 20) / (16 * dim)));
       const size_t pstride = dim * 2 * (size_t)TB;
-      const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * 8 + 2 * n * n + 4 * n) * sizeof(double));
+      const size_t sS = ctx->site_obs ? (size_t)site_stride(n) : 0;  // site sums per output
+      const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + sS) + 2 * n * n + 4 * n) * sizeof(double));
       size_t same = 0;
       while (idx + same < order.size() && ctx->probs[order[idx + same]].n_local == n) ++same;
       size_t cnt = (size_t)std::max(0.0, (budget - used) / per);
@@ -2109,10 +2212,12 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       J->Pm = ba.get<double>(pstride * cnt);
       J->Psi = ba.get<double>(pstride * cnt);
       J->obs = ba.get<double>((size_t)n_t * 8 * cnt);
+      J->sites = sS ? ba.get<double>((size_t)n_t * sS * cnt) : nullptr;
       const size_t tsz = (size_t)(2 * n * n + 5 * n);
       double* tabs = ba.get<double>(tsz * cnt);
       J->d_desc = ba.get<DenseProb>(cnt);
-      if (!J->V || !J->lam || !J->lam_lo || !J->diag_dd || !J->E || !J->info || !J->Pm || !J->Psi || !J->obs || !tabs || !J->d_desc) {
+      if (!J->V || !J->lam || !J->lam_lo || !J->diag_dd || !J->E || !J->info || !J->Pm || !J->Psi || !J->obs || !tabs || !J->d_desc ||
+          (sS && !J->sites)) {
         if (!jobs.empty()) break;  // this round is full: the register waits for the next one
         return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
       }
@@ -2145,6 +2250,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
         D.refine = ctx->dense_refine;
         D.obs = J->obs + (size_t)n_t * 8 * i;
         D.final_state = P.buf[0];
+        D.sites = sS ? J->sites + (size_t)n_t * sS * i : nullptr;
       }
       HIPC(hipMemcpyAsync(tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
       HIPC(hipMemcpyAsync(J->d_desc, desc.data(), desc.size() * sizeof(DenseProb), hipMemcpyHostToDevice, st));
@@ -2305,6 +2411,8 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
           const DenseProb* di = desc + i;
           auto per_block = [&](int tb0, int tb) -> int {
             if (launch_dense_obs_c(di, (int)dim, Psi, tb, tb0, st) != hipSuccess) return -1;
+            if (J.sites && launch_dense_obs_sites_c(di, (int)dim, Psi, tb, tb0, site_stride(J.n), st) != hipSuccess)
+              return -1;
             if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, Psi, tb, tau[n_t - 1], st) != hipSuccess)
               return -1;
             return 0;
@@ -2327,11 +2435,21 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
         if (rs != rocblas_status_success)
           return fail(ctx, DSE_ERR_HIP, "rocblas dgemm failed (status " + std::to_string((int)rs) + ")");
         HIPC(launch_dense_obs(desc, cnt, (int)dim, Psi, pstride, tb, tb0, st));
+        if (J.sites) HIPC(launch_dense_obs_sites(desc, cnt, (int)dim, Psi, pstride, tb, tb0, site_stride(J.n), st));
         if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, Psi, pstride, tb, tau[n_t - 1], st));
       }
       std::vector<double> h((size_t)n_t * 8 * cnt);
       HIPC(hipMemcpyAsync(h.data(), J.obs + (size_t)n_t * 8 * i0, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      std::vector<double> hs;
+      if (J.sites) {
+        hs.resize((size_t)n_t * site_stride(J.n) * cnt);
+        HIPC(hipMemcpyAsync(hs.data(), J.sites, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      }
       HIPC(hipStreamSynchronize(st));
+      for (int i = 0; i < cnt && J.sites; ++i)
+        for (int ti = 0; ti < n_t; ++ti)
+          finish_sites(J.n, hs.data() + ((size_t)i * n_t + ti) * site_stride(J.n),
+                       ctx->site_store[J.list[i]].data() + ti, (size_t)n_t);
       out_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - o0).count();
       for (int i = 0; i < cnt; ++i) {
         const int pi = J.list[i0 + i];
@@ -2478,6 +2596,10 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
                oDesc = take(sizeof(DenseProb)), oProb = take(sizeof(DevProb)),
                oCoef = take(std::max(row.size() * sizeof(double2), cf.size() * sizeof(double))), oErr = take(sizeof(int)),
                oCnt = take(nb * sizeof(int));
+  // option site_obs: the site sums of the same states, kept with the mode's other buffers (taken
+  // last and only with the option on: every other offset, and mx_cap with it off, as before)
+  const int sS = site_stride(n);
+  const size_t oSites = ctx->site_obs ? take((size_t)n_t * sS * sizeof(double)) : 0;
   if (off > ctx->mx_cap) {
     if (ctx->d_mx) (void)hipFree(ctx->d_mx), ctx->d_mx = nullptr;
     ctx->mx_cap = 0;
@@ -2583,8 +2705,15 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.n_sea = __builtin_popcountll(P.sea_mask);
   D.x0 = P.psi0;
   D.obs = d_obs;
+  if (ctx->site_obs) D.sites = reinterpret_cast<double*>(base + oSites);
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
+  std::vector<double> hsites;
+  if (D.sites) {
+    hsites.resize((size_t)n_t * sS);
+    HIPC(launch_dense_obs_sites_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, sS, st));
+    HIPC(hipMemcpyAsync(hsites.data(), D.sites, hsites.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
   HIPC(hipMemcpyAsync(P.buf[0], S + dim * (size_t)(n_t - 1), dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
   std::vector<double> h((size_t)n_t * 8);
   int herr = 0;
@@ -2594,6 +2723,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   if (herr) return fail(ctx, DSE_ERR_HIP, "propagator-matrix mode: column build failed");
   for (int ti = 0; ti < n_t; ++ti)
     finish_obs(P, h.data() + (size_t)ti * 8, obs_out + (size_t)pi * DSE_N_OBS * n_t + ti, (size_t)n_t);
+  for (int ti = 0; ti < n_t && D.sites; ++ti)
+    finish_sites(n, hsites.data() + (size_t)ti * sS, ctx->site_store[pi].data() + ti, (size_t)n_t);
   P.degree = deg;
   *h_apps = (double)deg * (double)dim;
   float b_ms = 0.f, p_ms = 0.f;
@@ -2671,6 +2802,61 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7) 
   if (ctx->probs[first].dist && (rc = xchg_allreduce_host(ctx, v, 7, st))) return rc;  // all shards
   finish_obs(ctx->probs[first], v, obs7, 1);
   ctx->evolved = false;
+  return DSE_OK;
+}
+
+int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out) {
+  if (!ctx) return DSE_ERR_ARG;
+  if (!psi || !out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  if (ctx->probs[first].dist)
+    return fail(ctx, DSE_ERR_ARG, "dse_site_observables: not available for a dist shard");
+  HIPC(hipSetDevice(ctx->device));
+  if ((rc = prepare(ctx))) return rc;
+  int64_t tiles = 0;
+  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
+  if ((rc = ensure_site_partial(ctx, 1))) return rc;
+  const size_t S = (size_t)ctx->site_S;
+  hipStream_t st = ctx->lanes[0].stream;
+  const double2* in = reinterpret_cast<const double2*>(psi);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    const size_t amps = size_t(1) << P.n_local;
+    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
+  }
+  int64_t off = 0;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    HIPC(launch_obs_sites(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_site_partial + off * S,
+                          (int)S, st));
+    off += P.n_tiles;
+  }
+  std::vector<double> h(tiles * S);
+  HIPC(hipMemcpyAsync(h.data(), ctx->d_site_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const int n = ctx->probs[first].n;
+  std::vector<double> v(S, 0.0);
+  for (int64_t t = 0; t < tiles; ++t)
+    for (int j = 0; j <= 3 * n; ++j) v[j] += h[t * S + j];
+  finish_sites(n, v.data(), out, 1);
+  ctx->evolved = false;
+  return DSE_OK;
+}
+
+int dse_site_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->site_nt : DSE_ERR_ARG; }
+
+int dse_get_site_obs(dse_ctx* ctx, int problem, double* out) {
+  if (!ctx) return DSE_ERR_ARG;
+  if (!out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  if (ctx->site_nt <= 0 || (size_t)problem >= ctx->site_store.size() ||
+      ctx->site_store[problem].size() != (size_t)3 * ctx->probs[problem].n * ctx->site_nt)
+    return fail(ctx, DSE_ERR_STATE, "no site observables (set option site_obs = 1 and call dse_evolve first)");
+  std::copy(ctx->site_store[problem].begin(), ctx->site_store[problem].end(), out);
   return DSE_OK;
 }
 
@@ -2894,6 +3080,12 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     }
   }
   for (auto& P : ctx->probs) any_big = any_big || !P.side();
+  if (ctx->site_obs)
+    for (auto& P : ctx->probs)
+      if (P.dist)
+        return fail(ctx, DSE_ERR_ARG, "site_obs: not available for a register partitioned over processes "
+                                      "(the all-reduce of the site sums is not implemented)");
+  reset_site_store(ctx, n_t);
   bool persistent = ctx->persistent != 0;
   bool any_dist = false;
   // spanning registers (options span / span_tile): every register that fits runs on k_span over
@@ -3618,8 +3810,17 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   double matrix_happl = 0.0;
   if (matrix_pi >= 0 && (rc = matrix_run(ctx, matrix_pi, t, n_t, matrix_dt, tol, obs_out, &matrix_happl))) return rc;
   phase("psi0/small");
-  const size_t chunk = (size_t)std::max<int64_t>(M, std::min<int64_t>(
+  size_t chunk = (size_t)std::max<int64_t>(M, std::min<int64_t>(
       n_t, std::max<int64_t>(1, (int64_t)(256ll << 20) / (ctx->total_items * 64))));
+  if (ctx->site_obs) {  // slots per flush: what both arenas hold under the same 256 MiB cap
+    int n_max = 1;
+    for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
+    const int64_t per_slot = ctx->total_items * (int64_t)site_stride(n_max) * 8;
+    chunk = std::min(chunk, (size_t)std::max<int64_t>(M, std::min<int64_t>(
+                                n_t, std::max<int64_t>(1, (int64_t)(256ll << 20) / per_slot))));
+    if ((rc = ensure_site_partial(ctx, chunk))) return rc;
+  }
+  const bool sites_on = ctx->site_obs != 0;
   if ((rc = ensure_partial(ctx, chunk))) return rc;
   if (ctx->time_every > 0)
     for (auto& ln : ctx->lanes) {
@@ -3670,10 +3871,15 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
         HIPC(hipEventRecord(ln.ev_iv[xq], ln.stream));
         HIPC(hipStreamWaitEvent(os, ln.ev_iv[xq], 0));
       }
-      for (auto& g : ln.groups)
+      for (auto& g : ln.groups) {
         HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
                         ctx->d_partial + (slot * ctx->total_items + g.off) * 8, os, n_out,
                         (size_t)ctx->total_items * 8, xq));
+        if (sites_on)
+          HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
+                                ctx->d_site_partial + (slot * ctx->total_items + g.off) * ctx->site_S,
+                                ctx->site_S, os, n_out, (size_t)ctx->total_items * ctx->site_S, xq));
+      }
       if (obs_ovl) {
         HIPC(hipEventRecord(ln.ev_obs[xq], os));
         ln.obs_pending[xq] = true;
@@ -3809,11 +4015,17 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     if (ctx->dbg & 1) {
       for (int j = 0; j < G.n_out; ++j) {
         for (auto& ln : ctx->lanes)
-          for (auto& g : ln.groups)
+          for (auto& g : ln.groups) {
             HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
                             j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
                             ctx->d_partial + ((slot + j) * ctx->total_items + g.off) * 8, ln.stream,
                             1, 0, q));
+            if (sites_on)
+              HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
+                                    j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
+                                    ctx->d_site_partial + ((slot + j) * ctx->total_items + g.off) * ctx->site_S,
+                                    ctx->site_S, ln.stream, 1, 0, q));
+          }
       }
     } else if ((rc = obs_all(q ? 0 : 2, slot, G.n_out, q))) {
       return rc;
@@ -3854,6 +4066,7 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   ctx->last_q = n_groups & 1;
   for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
   ctx->evolved = true;
+  if (ctx->site_obs) ctx->site_nt = n_t;  // the store is complete: dse_get_site_obs may read it
 
   if (stats) {
     double happl = small_happl + matrix_happl;
@@ -3880,6 +4093,9 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     stats->dense_ms = dense_ms;
     stats->dense_eig_ms = dense_eig_ms;
     stats->dense_nufft_problems = any_dense ? ctx->nufft_problems : 0;
+    int n_site = 0;
+    for (const auto& st : ctx->site_store) n_site += st.empty() ? 0 : 1;
+    stats->site_obs_problems = n_site;
     stats->dense_output_ms = any_dense ? ctx->dense_out_ms : 0.0;
     stats->step_kernel_ms = launches_timed > 0 ? step_ms : -1.0;
     stats->step_launches = launches + small_launches;
@@ -3914,6 +4130,10 @@ int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_o
   if (!ctx) return DSE_ERR_ARG;
   ctx->handoff_fallbacks = 0;
   ctx->eig_fallbacks = 0;
+  // the site observables of an earlier evolve end here, whatever becomes of this call (an argument
+  // error before any work, a failure half way): dse_get_site_obs is DSE_ERR_STATE until an evolve
+  // with the option on has succeeded
+  ctx->site_nt = 0;
   int rc = evolve_impl(ctx, t, n_t, tol, obs_out, stats);
   int* const d_err = ctx->d_err_cur;
   ctx->d_err_cur = nullptr;

@@ -9,6 +9,9 @@
 namespace dse {
 
 constexpr int kSmallMaxQubits = 9;
+// site-resolved sums per problem and output (option site_obs): X_b Y_b Z_b at [3 b + c], ||psi||^2
+// at [3 n], padded to an even count for n = 9
+constexpr int kSmallSiteStride = 28;
 
 struct SmallProb {
   double2* state;          // [2^n] the state at the start of the next launch
@@ -26,9 +29,10 @@ struct SmallProb {
 // One launch: intervals m0 .. m0 + n_int - 1 of problems sel[0 .. count) (all with n qubits);
 // out[problem][m + 1][8] = raw observable sums of psi(t_{m+1}) (dse_runtime.hip finish_obs).
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
-                        const int* iv_set, double* out, hipStream_t st);
+                        const int* iv_set, double* out, hipStream_t st, double* sites = nullptr);
 // out[problem][0][8] = observable sums of the state buffer (psi0)
+// sites non-null (both launches): also sites[problem][m][kSmallSiteStride], the site-resolved sums
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st);
+                             hipStream_t st, double* sites = nullptr);
 
 }  // namespace dse

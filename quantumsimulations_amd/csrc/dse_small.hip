@@ -29,10 +29,56 @@ struct SmallGeo {
   static constexpr int NP = N * (N - 1) / 2;
 };
 
+// Site-resolved sums of the state in LDS w (option site_obs): X_b Y_b Z_b at o[3 b + c] for every
+// bit b < N, ||psi||^2 at o[3 N], zero up to kSmallSiteStride; each sum one wave butterfly.
 template <int N>
+__device__ __forceinline__ void small_site_sums(const double2* w, int lane, bool live, double* o) {
+  constexpr int R = SmallGeo<N>::R;
+  double n2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double2 p = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
+    n2 += p.x * p.x + p.y * p.y;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+  if (lane == 0) o[3 * N] = n2;
+  if (lane > 0 && 3 * N + lane < kSmallSiteStride) o[3 * N + lane] = 0.0;
+  for (int b = 0; b < N; ++b) {
+    double v[3] = {0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int x = r * 64 + lane;
+      if (!live) continue;
+      const double2 p = w[x];
+      const double p2 = p.x * p.x + p.y * p.y;
+      if ((x >> b) & 1) {
+        v[2] -= 0.5 * p2;
+        continue;
+      }
+      v[2] += 0.5 * p2;
+      const double2 s = w[x ^ (1 << b)];
+      v[0] += p.x * s.x + p.y * s.y;
+      v[1] += p.x * s.y - p.y * s.x;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    if (lane == 0) {
+      o[3 * b] = v[0];
+      o[3 * b + 1] = v[1];
+      o[3 * b + 2] = v[2];
+    }
+  }
+}
+
+// SITES: also the site-resolved sums of every output into sites[problem][m][kSmallSiteStride]
+// (the 7 aggregate sums keep their code and order)
+template <int N, bool SITES>
 __global__ void __launch_bounds__(64)
 k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0, int n_int,
-        const int* __restrict__ iv_set, double* __restrict__ out) {
+        const int* __restrict__ iv_set, double* __restrict__ out, double* __restrict__ sites) {
   using G = SmallGeo<N>;
   constexpr int R = G::R, DIM = G::DIM, NP = G::NP;
   __shared__ double2 w[DIM];
@@ -192,6 +238,8 @@ k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0
     }
     __syncthreads();
     if (lane < 8) out[((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * 8 + lane] = lane < 7 ? red[lane] : 0.0;
+    if (SITES)
+      small_site_sums<N>(w, lane, live, sites + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallSiteStride);
     __syncthreads();
   }
 #pragma unroll
@@ -200,9 +248,10 @@ k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0
 }
 
 // observables of the initial state (output 0)
-template <int N>
+template <int N, bool SITES>
 __global__ void __launch_bounds__(64)
-k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, double* __restrict__ out) {
+k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, double* __restrict__ out,
+             double* __restrict__ sites) {
   using G = SmallGeo<N>;
   constexpr int R = G::R, DIM = G::DIM;
   __shared__ double2 w[DIM];
@@ -244,6 +293,7 @@ k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, d
     for (int j = 0; j < 7; ++j) o[j] = v[j];
     o[7] = 0.0;
   }
+  if (SITES) small_site_sums<N>(w, lane, live, sites + (size_t)sel[blockIdx.x] * P.n_t * kSmallSiteStride);
 }
 
 }  // namespace
@@ -251,11 +301,18 @@ k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, d
 #define DSE_SMALL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
 
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
-                        const int* iv_set, double* out, hipStream_t st) {
+                        const int* iv_set, double* out, hipStream_t st, double* sites) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
-  case q: hipLaunchKernelGGL((k_small<q>), dim3(count), dim3(64), 0, st, probs, sel, m0, n_int, iv_set, out); break;
+  case q:                                                                                                      \
+    if (sites)                                                                                                 \
+      hipLaunchKernelGGL((k_small<q, true>), dim3(count), dim3(64), 0, st, probs, sel, m0, n_int, iv_set, out, \
+                         sites);                                                                               \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_small<q, false>), dim3(count), dim3(64), 0, st, probs, sel, m0, n_int, iv_set,     \
+                         out, sites);                                                                          \
+    break;
     DSE_SMALL_CASES(X)
 #undef X
     default:
@@ -265,11 +322,16 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 }
 
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st) {
+                             hipStream_t st, double* sites) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
-  case q: hipLaunchKernelGGL((k_small_obs0<q>), dim3(count), dim3(64), 0, st, probs, sel, out); break;
+  case q:                                                                                                  \
+    if (sites)                                                                                             \
+      hipLaunchKernelGGL((k_small_obs0<q, true>), dim3(count), dim3(64), 0, st, probs, sel, out, sites);   \
+    else                                                                                                   \
+      hipLaunchKernelGGL((k_small_obs0<q, false>), dim3(count), dim3(64), 0, st, probs, sel, out, sites);  \
+    break;
     DSE_SMALL_CASES(X)
 #undef X
     default:

@@ -33,11 +33,11 @@ from .model import (  # noqa: F401  (re-exported API)
     get_derived_frequencies,
     shell_positions_with_rare_center,
 )
-from .problem import OBS_NAMES, Problem, build_problem, time_grid
+from .problem import OBS_NAMES, Problem, build_problem, site_traces_from_bits, time_grid
 
 __all__ = [
     "DipolarRareParams", "get_derived_frequencies", "shell_positions_with_rare_center",
-    "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch",
+    "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch", "simulate_rare_sites",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
 ]
 
@@ -70,9 +70,16 @@ def dims_with_rare(n_sea: int, is_spin_three_half: bool = False) -> List[int]:
     return [2] * n_sea + ([4] if is_spin_three_half else [2])
 
 
-def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | None = None
-                        ) -> List[Tuple[np.ndarray, Dict[str, np.ndarray]]]:
-    """Many evolutions at once on one device (same results as calling simulate_rare on each)."""
+SITE_NAMES: Tuple[str, ...] = ("Ix", "Iy", "Iz")
+
+
+def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | None = None,
+                        site_resolved: bool = False) -> List[Tuple]:
+    """Many evolutions at once on one device (same results as calling simulate_rare on each).
+
+    ``site_resolved=True``: every result is ``(t, obs, sites)`` with ``sites = {"Ix", "Iy", "Iz"}``,
+    each ``(n_sites, steps)`` by reference site index (see simulate_rare_sites); ``t`` and ``obs``
+    are what the default call returns."""
     device = _default_device() if device is None else device
     grids = [time_grid(p) for p in params_list]       # raises ValueError like :620-621
     probs = [build_problem(p, order="engine", reduce=True) for p in params_list]
@@ -89,9 +96,22 @@ def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | 
             for i in members:
                 eng.add(probs[i])
             t = grids[members[0]]
-            obs, _ = eng.evolve(t, tol=_tol())
+            if site_resolved:
+                # only for this call: the cached engine is shared with the default path
+                eng.set_option("site_obs", 1)
+            try:
+                obs, _ = eng.evolve(t, tol=_tol())
+                traces = [eng.site_traces(slot) for slot in range(len(members))] if site_resolved else None
+            finally:
+                if site_resolved:
+                    eng.set_option("site_obs", 0)
             for slot, i in enumerate(members):
                 results[i] = (t.copy(), {name: obs[slot, j].copy() for j, name in enumerate(OBS_NAMES)})
+                if site_resolved:
+                    p = probs[i]
+                    by_site = site_traces_from_bits(traces[slot], p.site_of_bit, p.n_sites, p.reduced,
+                                                    p.rare_z_const)
+                    results[i] += ({name: by_site[c].copy() for c, name in enumerate(SITE_NAMES)},)
     eng.clear()
     return results
 
@@ -106,6 +126,18 @@ def simulate_rare(params: DipolarRareParams) -> Tuple[np.ndarray, Dict[str, np.n
     checked offline (QuTiP is absent: parity unpinned); the sweep always sets the overrides
     (sweep_sea_detuning.py:1247-1250), where both return one norm per output time."""
     return simulate_rare_batch([params])[0]
+
+
+def simulate_rare_sites(params: DipolarRareParams
+                        ) -> Tuple[np.ndarray, Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+    """simulate_rare plus the site-resolved traces: ``(t, obs, sites)``.
+
+    ``sites = {"Ix": (n_sites, steps), "Iy": ..., "Iz": ...}``: <Ix_k>, <Iy_k>, <Iz_k> of the
+    normalised state for every site k in the reference's site order (sea sites 0 .. n_sea - 1, the
+    rare site last).  When the rare spin is frozen (center geometry, not driven: the register holds
+    only the sea spins) its row is the constant Iz = -init_x_sign / 2, Ix = Iy = 0, as ``obs["Iz_R"]``.
+    No reference counterpart: the reference returns only the seven aggregates."""
+    return simulate_rare_batch([params], site_resolved=True)[0]
 
 
 def problem_to_csr(prob: Problem) -> sp.csr_matrix:

@@ -240,6 +240,28 @@ class Engine:
                                        C.byref(st)))
         return out, st.as_dict()
 
+    def site_observables(self, pid: int, psi: np.ndarray) -> np.ndarray:
+        """(3, n): <Ix_b>, <Iy_b>, <Iz_b> of every register bit b of the normalised state ``psi``
+        (dse_site_observables: the kernel of the option "site_obs", whatever its value)."""
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        out = np.empty((3, self.problems[pid].n_qubits))
+        self._check(self._L.dse_site_observables(self._h, pid, _lib.ptr(x), _lib.ptr(out)))
+        return out
+
+    def site_traces(self, pid: int) -> np.ndarray:
+        """(3, n, n_t): the site-resolved traces of register ``pid`` from the last evolve, which
+        must have run with the option "site_obs" = 1 (RuntimeError otherwise)."""
+        if not 0 <= pid < len(self.problems):
+            raise ValueError("bad problem id")
+        # sized from what the library holds (0: none; the call below then raises and writes nothing)
+        n_t = max(int(self._L.dse_site_obs_outputs(self._h)), 0)
+        out = np.empty((3, self.problems[pid].n_qubits, max(n_t, 1)))
+        self._check(self._L.dse_get_site_obs(self._h, pid, _lib.ptr(out)))
+        return out
+
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
         self._check(self._L.dse_get_state(self._h, pid, _lib.ptr(out)))

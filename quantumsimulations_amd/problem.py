@@ -201,6 +201,28 @@ def build_problem(params: DipolarRareParams, order: str = "engine", reduce: bool
                    site_of_bit, n_sites, reduced, order, meta)
 
 
+def site_traces_from_bits(bit_traces: np.ndarray, site_of_bit: np.ndarray, n_sites: int, reduced: bool,
+                          rare_z_const: float) -> np.ndarray:
+    """Site-resolved traces by reference site index from traces by register bit.
+
+    ``bit_traces`` is ``(3, n, ...)`` (components Ix, Iy, Iz of bit b); the result is
+    ``(3, n_sites, ...)`` with row ``site_of_bit[b]`` = bit b.  In a reduced register the frozen rare
+    spin (the last site) is not a bit: its row is Iz = ``rare_z_const``, Ix = Iy = 0, as the
+    engine reports ``Iz_R`` there.  Pure numpy (no device)."""
+    bt = np.asarray(bit_traces, dtype=np.float64)
+    sob = np.asarray(site_of_bit, dtype=np.int64)
+    if bt.ndim < 2 or bt.shape[0] != 3 or bt.shape[1] != sob.shape[0]:
+        raise ValueError("bit_traces must have shape (3, n, ...) with n = len(site_of_bit)")
+    expect = n_sites - 1 if reduced else n_sites
+    if sob.shape[0] != expect or sorted(sob.tolist()) != list(range(expect)):
+        raise ValueError("site_of_bit must be a permutation of the register's sites")
+    out = np.zeros((3, n_sites) + bt.shape[2:])
+    out[:, sob] = bt
+    if reduced:
+        out[2, n_sites - 1] = rare_z_const
+    return out
+
+
 def spectral_bounds(prob: Problem) -> Tuple[float, float]:
     """Rigorous [E_min, E_max] of H by Weyl's inequality over one- and two-qubit pieces.
 

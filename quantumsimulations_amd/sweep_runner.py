@@ -107,13 +107,16 @@ _atexit.register(close_engines)
 
 
 def evolve_many(params_list: Sequence[DipolarRareParams], devices: Optional[Sequence[int]] = None,
-                tol: Optional[float] = None) -> List[Trace]:
+                tol: Optional[float] = None, site_resolved: bool = False) -> List[Trace]:
     """``simulate_rare`` for every parameter set, spread over ``devices`` (one host thread and one
     libdse context per GPU; the ctypes call releases the GIL).  Results in input order.  Each
     device evolves its share in batches that fit its free memory (the reference runs one
     evolution at a time, so a sweep of large registers must not allocate all of them at once).
-    ``tol``: Chebyshev truncation, default DSE_TOL as in simulate_rare."""
-    from .dipolar_ensemble_with_rare import _tol
+    ``tol``: Chebyshev truncation, default DSE_TOL as in simulate_rare.
+    ``site_resolved``: every result is ``(t, obs, sites)``, ``sites = {"Ix", "Iy", "Iz"}`` of shape
+    ``(n_sites, steps)`` by reference site index (simulate_rare_sites); ``t`` and ``obs`` unchanged."""
+    from .dipolar_ensemble_with_rare import SITE_NAMES, _tol
+    from .problem import site_traces_from_bits
     tol = _tol() if tol is None else float(tol)
     grids = [time_grid(p) for p in params_list]
     probs = [build_problem(p, order="engine", reduce=True) for p in params_list]
@@ -148,10 +151,22 @@ def evolve_many(params_list: Sequence[DipolarRareParams], devices: Optional[Sequ
                     for i in members:
                         eng.add(probs[i])
                     t = grids[members[0]]
-                    obs, _ = eng.evolve(t, tol=tol)
+                    if site_resolved:  # for this evolve only: the cached engine is shared
+                        eng.set_option("site_obs", 1)
+                    try:
+                        obs, _ = eng.evolve(t, tol=tol)
+                        bits = [eng.site_traces(slot) for slot in range(len(members))] if site_resolved else None
+                    finally:
+                        if site_resolved:
+                            eng.set_option("site_obs", 0)
                     for slot, i in enumerate(members):
                         results[i] = (t.copy(), {name: obs[slot, j].copy()
                                                  for j, name in enumerate(OBS_NAMES)})
+                        if site_resolved:
+                            p = probs[i]
+                            by_site = site_traces_from_bits(bits[slot], p.site_of_bit, p.n_sites, p.reduced,
+                                                            p.rare_z_const)
+                            results[i] += ({name: by_site[c].copy() for c, name in enumerate(SITE_NAMES)},)
             eng.clear()
         except BaseException as exc:  # re-raised in the caller's thread
             errors.append(exc)
@@ -331,6 +346,9 @@ def write_sweep(plan: SweepPlan, traces: Sequence[Trace], report: str = "full",
                 details_out: Optional[list] = None, workers: Optional[int] = None) -> str:
     """Per-point files and metrics in detuning order, the report, global_params.json and
     summary.json (:611-1157) from the evolutions' traces (in ``plan.flat`` order).
+    Traces that carry a third element (evolve_many's ``site_resolved``) additionally give
+    ``time_and_site_obs_{tag}.npz`` per point (t, Ix_site, Iy_site, Iz_site: float64,
+    ``(n_sites, steps)``); every other file is unchanged.
     ``details_out``: receives the (det_dir, per, metrics, det) rows a report is drawn from.
     ``workers`` (default writer_count()): with more than one and at least 8 points, the per-point
     PNGs (most of a report's time: ~1.4 s per point at 300 dpi) are drawn by that many spawned
@@ -347,9 +365,13 @@ def write_sweep(plan: SweepPlan, traces: Sequence[Trace], report: str = "full",
         os.makedirs(det_dir, exist_ok=True)
         per = {}
         for j, tag in enumerate(VARIANTS):
-            t_arr, obs = traces[3 * idx + j]
+            t_arr, obs = traces[3 * idx + j][:2]
             p = plan.point_params[idx][tag]
             np.savez(os.path.join(det_dir, f"time_and_obs_{tag}.npz"), t=t_arr, **obs)
+            if len(traces[3 * idx + j]) > 2:
+                sites = traces[3 * idx + j][2]
+                np.savez(os.path.join(det_dir, f"time_and_site_obs_{tag}.npz"), t=t_arr,
+                         **{f"{c}_site": np.asarray(sites[c], dtype=np.float64) for c in ("Ix", "Iy", "Iz")})
             _json_dump(os.path.join(det_dir, f"params_{tag}.json"), asdict(p))
             _json_dump(os.path.join(det_dir, f"freqs_{tag}.json"), get_derived_frequencies(p))
             per[tag] = (t_arr, obs)
@@ -419,11 +441,13 @@ def run_sweep_sea_detuning(
     report: str = "full",
     timings: Optional[Dict[str, float]] = None,
     verbose: bool = True,
+    site_resolved: bool = False,
 ) -> str:
     """Same arguments, outputs and return value (the sweep directory) as
     sweep_sea_detuning.py:356-1165, plus ``devices`` (GPU ids, default all visible),
-    ``report`` ("full" | "png" | "none") and ``timings`` (filled with evolve_s / outputs_s /
-    report_s)."""
+    ``report`` ("full" | "png" | "none"), ``timings`` (filled with evolve_s / outputs_s /
+    report_s) and ``site_resolved`` (each point also writes ``time_and_site_obs_{tag}.npz``: the
+    per-site <Ix>, <Iy>, <Iz> traces; every other file as without it)."""
     if report not in ("full", "png", "none"):
         raise ValueError(f"report must be 'full', 'png' or 'none', not {report!r}")
     plan = plan_sweep(f_Az=f_Az, f1A=f1A, target_sea_detuning=target_sea_detuning,
@@ -433,7 +457,8 @@ def run_sweep_sea_detuning(
                       solver_atol=solver_atol, solver_rtol=solver_rtol, solver_nsteps=solver_nsteps,
                       solver_max_step=solver_max_step, coarse_window=coarse_window, verbose=verbose)
     t0 = time.perf_counter()
-    traces = evolve_many(plan.flat, devices)
+    # (the default call is the one it always was: callers substitute evolve_many by its old signature)
+    traces = evolve_many(plan.flat, devices, site_resolved=True) if site_resolved else evolve_many(plan.flat, devices)
     t1 = time.perf_counter()
     if verbose:
         print(f"  evolved {len(plan.flat)} evolutions in {t1 - t0:.2f} s", flush=True)
