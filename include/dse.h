@@ -39,6 +39,11 @@ extern "C" {
 #endif
 
 #define DSE_ABI_VERSION 14
+/* Additions that leave every existing entry as it is (new functions, fields appended to dse_stats)
+ * raise the minor number; a caller checks dse_abi_version() == DSE_ABI_VERSION and
+ * dse_abi_minor() >= the DSE_ABI_MINOR it was built against.  14.1: initial states other than a
+ * basis state (dse_set_initial_state, ...; dse_stats.custom_init_problems). */
+#define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
 
@@ -122,10 +127,15 @@ typedef struct dse_stats {
                               /* "site_obs"; a loopback partitioned register counts once; ABI 14) */
   double dense_output_ms;     /* host wall time of the dense engine's output stage (refinement,   */
                               /* transform or GEMM, observables)                                   */
+  int32_t custom_init_problems; /* registers this call started from anything other than the basis  */
+                              /* state psi0_index (dse_set_initial_state / _product /              */
+                              /* dse_continue_from_final; a loopback partitioned register counts   */
+                              /* once; ABI 14.1)                                                   */
 } dse_stats;
 
 /* ---- library / device ------------------------------------------------------------------- */
 int dse_abi_version(void);
+int dse_abi_minor(void);
 int dse_device_count(void);                 /* number of HIP devices, 0 if none              */
 /* free_total[0] = free, free_total[1] = total device memory in bytes (hipMemGetInfo), so a caller
  * can batch evolutions to fit HBM. */
@@ -342,9 +352,10 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7);
  * kernel of the option "site_obs" whatever the option's value; a loopback partitioned register:
  * shard 0's id and the whole 2^n state; not available for a dist shard, DSE_ERR_ARG). */
 int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out);
-/* Evolves every problem from its basis state psi0 at t[0] through the output times t[0..n_t)
- * (strictly increasing) with an exact Chebyshev propagator (truncation tolerance tol, e.g.
- * 1e-14) and writes obs_out[problem][DSE_N_OBS][n_t].  stats may be NULL. */
+/* Evolves every problem from its initial state at t[0] (the basis state psi0, or the state set by
+ * dse_set_initial_state / dse_set_initial_product / dse_continue_from_final) through the output
+ * times t[0..n_t) (strictly increasing) with an exact Chebyshev propagator (truncation tolerance
+ * tol, e.g. 1e-14) and writes obs_out[problem][DSE_N_OBS][n_t].  stats may be NULL. */
 int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_out,
                dse_stats* stats);
 /* After dse_evolve with option "site_obs" = 1: out[3][n][n_t], component 0 Ix, 1 Iy, 2 Iz of
@@ -358,6 +369,45 @@ int dse_get_site_obs(dse_ctx* ctx, int problem, double* out);
 int dse_site_obs_outputs(const dse_ctx* ctx);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);
+/* ---- initial states other than a basis state (ABI 14.1) --------------------------------------
+ * The reference prepares psi0 as a basis ket (:591-606); these entries let an evolution start from
+ * any state: a product state after a pulse, the previous segment's final state of a pulse sequence,
+ * a random state, a checkpoint.  The initial state belongs to the problem: it persists over
+ * repeated dse_evolve calls (each starts from it again at t[0]) and is dropped by dse_clear.  It is
+ * not normalised: state_norm reports its norm at every output, the expectations are of the
+ * normalised state as everywhere else.
+ *   - A stored state (dse_set_initial_state, dse_continue_from_final) lives in ONE extra device
+ *     buffer of the state's size per register, allocated only for problems that have one; a
+ *     product state keeps its 4 n doubles only.  With no custom initial state in the context
+ *     nothing is allocated and no kernel beyond the basis-state path is launched.
+ *   - No engine choice reads the initial state: a register runs on the engine it would run on from
+ *     its basis state (k_small, the streaming / Walsh-Hadamard / k_interval / k_span / k_real
+ *     Chebyshev paths, the dense engine with GEMM or non-uniform-FFT outputs, propagator-matrix
+ *     mode, loopback shards), and from the basis state every result is bitwise what it was.  There
+ *     are no exceptions.  (The Python host's frozen-rare reduction assumes the basis state; its
+ *     helpers for general states build the unreduced register, see simulate_rare_from.)
+ *   - The re-run after a hand-off timeout (stats handoff_fallbacks) starts from the same state.
+ *   - Loopback partitioned registers (shard_rank = -1): shard 0's id and the whole 2^n state; the
+ *     id of another shard is DSE_ERR_ARG.  A register partitioned over processes
+ *     (shard_rank >= 0) is not supported: DSE_ERR_ARG.
+ *   - Errors: DSE_ERR_ARG for a bad id, a non-finite or all-zero state or amplitude pair;
+ *     DSE_ERR_OOM if a buffer cannot be allocated (the problem keeps its previous initial state).
+ *
+ * psi: 2^n interleaved complex.  The problem's later dse_evolve calls start from it at t[0].
+ * NULL: back to the basis state psi0_index (the extra buffer is released). */
+int dse_set_initial_state(dse_ctx* ctx, int problem, const double* psi);
+/* Product state: amp[4 b + (0..3)] = (re a_b0, im a_b0, re a_b1, im a_b1);
+ * psi(x) = prod_b a_b[bit_b(x)], built on the device by k_product_state at every dse_evolve
+ * (nothing state-sized crosses the host; a shard writes its global indices (shard << n_local) | x). */
+int dse_set_initial_product(dse_ctx* ctx, int problem, const double* amp /* [4n] */);
+/* The final state of the last dse_evolve, which must have returned DSE_OK, becomes this problem's
+ * initial state (device-to-device copy; DSE_ERR_STATE without such an evolve, or after a hook
+ * call that used the state buffers).  Continuation of a run over t[k..], checkpoints. */
+int dse_continue_from_final(dse_ctx* ctx, int problem);
+/* The state the next dse_evolve would start from (the basis state, the stored state, or the
+ * product state materialised by its kernel): test and diagnostic hook. */
+int dse_get_initial_state(dse_ctx* ctx, int problem, double* psi_out);
+
 /* Energy of the final state after dse_evolve, on the device: e_out[0] = <psi|H|psi> / <psi|psi>,
  * e_out[1] = <psi|psi> (a partitioned loopback register: shard 0's id, whole register).  Unitary
  * evolution conserves both exactly, so they check a run whose state is too large to compare

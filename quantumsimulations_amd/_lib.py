@@ -21,6 +21,7 @@ DSE_ERR_STATE = -5
 DSE_ERR_NODEVICE = -6
 DSE_N_OBS = 7
 DSE_ABI_VERSION = 14
+DSE_ABI_MINOR = 1    # additions since 14.0: the initial-state entries, DseStats.custom_init_problems
 
 EXPORTED = (
     "dse_abi_version", "dse_device_count", "dse_spectral_bounds", "dse_bessel_j",
@@ -29,7 +30,8 @@ EXPORTED = (
     "dse_evolve", "dse_get_state", "dse_time_step_kernel", "dse_add_problem_sharded",
     "dse_dist_unique_id", "dse_dist_init", "dse_problem_dim", "dse_wht_plan", "dse_energy",
     "dse_device_memory", "dse_dist_init_exchange", "dse_site_observables", "dse_get_site_obs",
-    "dse_site_obs_outputs",
+    "dse_site_obs_outputs", "dse_set_initial_state", "dse_set_initial_product",
+    "dse_continue_from_final", "dse_get_initial_state", "dse_abi_minor",
 )
 DSE_DIST_ID_BYTES = 128
 DSE_XCHG_ALLTOALL, DSE_XCHG_SENDRECV, DSE_XCHG_ALLREDUCE_F64 = 1, 2, 3
@@ -75,6 +77,7 @@ class DseStats(C.Structure):
         ("dense_nufft_problems", C.c_int32),
         ("site_obs_problems", C.c_int32),
         ("dense_output_ms", C.c_double),
+        ("custom_init_problems", C.c_int32),
     ]
 
     def as_dict(self):
@@ -91,6 +94,7 @@ _vp = C.c_void_p
 def _declare(lib):
     sig = {
         "dse_abi_version": (C.c_int, []),
+        "dse_abi_minor": (C.c_int, []),
         "dse_device_count": (C.c_int, []),
         "dse_spectral_bounds": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp]),
         "dse_bessel_j": (C.c_int, [C.c_double, C.c_int, _dp, C.c_double, C.POINTER(C.c_int)]),
@@ -110,6 +114,10 @@ def _declare(lib):
         "dse_site_observables": (C.c_int, [_vp, C.c_int, _dp, _dp]),
         "dse_get_site_obs": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_site_obs_outputs": (C.c_int, [_vp]),
+        "dse_set_initial_state": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_set_initial_product": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_continue_from_final": (C.c_int, [_vp, C.c_int]),
+        "dse_get_initial_state": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_energy": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_device_memory": (C.c_int, [C.c_int, _dp]),
         "dse_dist_init_exchange": (C.c_int, [_vp, C.c_int, C.c_int, EXCHANGE_FN, C.c_void_p]),
@@ -140,8 +148,11 @@ def lib():
                     f"{path} is missing: build it with `python -m quantumsimulations_amd.build` "
                     "(the HIP engine has no CPU fallback)")
             handle = C.CDLL(path)
+            # a library from before 14.1 has no dse_abi_minor (nor the entries declared below)
+            if not hasattr(handle, "dse_abi_minor"):
+                raise ImportError("libdse.so predates ABI 14.1; rebuild it")
             _declare(handle)
-            if handle.dse_abi_version() != DSE_ABI_VERSION:
+            if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
             _lib = handle
     return _lib

@@ -47,6 +47,12 @@ struct DenseProb {
   double* obs;          // [n_t][8] raw observable sums of this problem (finish_obs order)
   double2* final_state; // [dim] psi(t_last) in the reference frame (dse_get_state), or null
   double* sites;        // option site_obs: [n_t][S] raw site sums (k_dense_obs_sites), else null
+  // custom psi(t0) (ABI 14.1): init = psi0 in the reference frame (dim amplitudes, read before the
+  // final state is written: it may alias final_state), c = [Re c | Im c] (2 dim) of c = V^T phi0,
+  // phi0_x = i^|x| psi0_x (rot) written by launch_dense_project; x0 is then 0.  Both null: psi(t0) =
+  // e_x0, c the row x0 of V (every kernel as it was)
+  const double2* init;
+  double* c;
 };
 
 // H' of every problem into its (zeroed) V
@@ -61,6 +67,12 @@ hipError_t launch_dense_rq(const DenseProb* d, int count, int dim, hipStream_t s
 // P[a + (tb + j) dim] = -c_a sin(lambda_a tau_j); problem p's block at P + p * pstride
 hipError_t launch_dense_phase(const DenseProb* d, int count, int dim, const double* tau, int tb,
                               double* P, size_t pstride, hipStream_t st);
+// custom psi(t0): c = V^T phi0 of every problem with DenseProb::c (dse_init.hip), and the phase
+// columns of those problems, P[a + j dim] = c_r cos + c_i sin, P[a + (tb + j) dim] = c_i cos - c_r sin
+// (after launch_dense_phase, which serves the others)
+hipError_t launch_dense_project(const DenseProb* d, int count, int dim, hipStream_t st);
+hipError_t launch_dense_phase_c(const DenseProb* d, int count, int dim, const double* tau, int tb,
+                                double* P, size_t pstride, hipStream_t st);
 // observables of the tb columns of Psi' (re | im blocks as P) into d[p].obs rows t0 .. t0 + tb
 hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
                             int tb, int t0, hipStream_t st);
@@ -112,12 +124,14 @@ struct NufftCache;  // rocFFT plans (per context)
 void nufft_release(NufftCache* c);
 size_t nufft_scratch_doubles(const NufftGrid& g, int dim);
 // psi' of every output of one register (V column-major dim x dim, eigenvalues lam_hi + lam_lo,
-// psi0 = e_x0; lam_lo null: the unrefined eigenvalues, low parts zero, no device read of them)
+// psi0 = e_x0, or with c_custom (device, [Re c | Im c], 2 dim doubles) the custom psi0 whose
+// coefficients launch_dense_project wrote; lam_lo null: the unrefined eigenvalues, low parts zero,
+// no device read of them)
 // into Psi in blocks of TB interleaved complex columns, per_block(tb0, tb) called after each block
 // (the observables, the final state); 0 on success
 int nufft_outputs(NufftCache*& cache, hipStream_t st, const NufftGrid& g, const NufftScratch& S, const double* V,
                   const double* lam_hi, const double* lam_lo, uint64_t x0, int dim, double* Psi, int TB,
-                  const std::function<int(int tb0, int tb)>& per_block);
+                  const std::function<int(int tb0, int tb)>& per_block, const double* c_custom = nullptr);
 
 }  // namespace dse
 

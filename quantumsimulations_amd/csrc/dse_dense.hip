@@ -202,6 +202,27 @@ k_dense_phase(const DenseProb* __restrict__ probs, int dim, const double* __rest
   blk[a + (size_t)j * dim] = c * co;
   blk[a + (size_t)(tb + j) * dim] = -c * s;
 }
+
+// The same columns for the problems with a custom psi(t0) (DenseProb::c = [Re c | Im c] of the
+// complex c = V^T phi0): c e^{-i lam tau} = (c_r cos + c_i sin) + i (c_i cos - c_r sin).  Problems
+// without one are left to k_dense_phase.
+__global__ void __launch_bounds__(256)
+k_dense_phase_c(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ tau, int tb,
+                double* __restrict__ Pm, size_t pstride) {
+  const DenseProb& P = probs[blockIdx.z];
+  const uint32_t a = blockIdx.x * 256u + threadIdx.x;
+  const int j = blockIdx.y;
+  if (!P.c || a >= (uint32_t)dim) return;
+  const double cr = P.c[a], ci = P.c[(size_t)dim + a];
+  double s, co;
+  if (P.refine)
+    dd_sincos(P.lam[a], P.lam_lo[a], tau[j], &s, &co);
+  else
+    sincos(P.lam[a] * tau[j], &s, &co);
+  double* blk = Pm + blockIdx.z * pstride;
+  blk[a + (size_t)j * dim] = cr * co + ci * s;
+  blk[a + (size_t)(tb + j) * dim] = ci * co - cr * s;
+}
 #pragma clang fp contract(fast)
 
 // block sum of 7 values (256 threads = 4 waves)
@@ -369,6 +390,13 @@ hipError_t launch_dense_rq(const DenseProb* d, int count, int dim, hipStream_t s
 hipError_t launch_dense_phase(const DenseProb* d, int count, int dim, const double* tau, int tb,
                               double* P, size_t pstride, hipStream_t st) {
   hipLaunchKernelGGL(k_dense_phase, dim3((dim + 255) / 256, tb, count), dim3(256), 0, st, d, dim, tau,
+                     tb, P, pstride);
+  return hipGetLastError();
+}
+
+hipError_t launch_dense_phase_c(const DenseProb* d, int count, int dim, const double* tau, int tb,
+                                double* P, size_t pstride, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_phase_c, dim3((dim + 255) / 256, tb, count), dim3(256), 0, st, d, dim, tau,
                      tb, P, pstride);
   return hipGetLastError();
 }

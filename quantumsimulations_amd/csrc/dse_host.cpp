@@ -14,6 +14,7 @@
 #include "../../include/dse.h"
 
 extern "C" int dse_abi_version(void) { return DSE_ABI_VERSION; }
+extern "C" int dse_abi_minor(void) { return DSE_ABI_MINOR; }
 
 extern "C" int dse_spectral_bounds(int n, const double* field, const double* zz, const double* pair,
                                    const double* flip, double shift, double* e_min, double* e_max) {

@@ -184,11 +184,13 @@ constexpr int kRealRegPairs = kRealRB * (kRealRB - 1) / 2;
 __host__ __device__ constexpr int real_rr_index(int a, int b) {  // a < b < kRealRB
   return a * (2 * kRealRB - a - 1) / 2 + (b - a - 1);
 }
+constexpr uint64_t kRealFromBuffer = ~uint64_t(0);
 struct alignas(16) RealTab {
   double rr_g[kRealRegPairs];  // rotated pair coefficients (-g) among register bits
   double rflip[kRealRB][2];    // rotated drive of register bit i, by output value (0, 1)
-  uint64_t x0;                 // psi(t0) = e_x0
-  int x0pop;                   // popcount(x0): psi = i^{|x0| - |x|} phi
+  uint64_t x0;                 // psi(t0) = e_x0; kRealFromBuffer: a custom psi(t0), split from the
+                               // state buffer by k_real_split (phi0_x = i^|x| psi0_x)
+  int x0pop;                   // popcount(x0): psi = i^{|x0| - |x|} phi (0 with a custom psi(t0))
   int rflip_mask;
   // coefficient row of iteration j (thread bit j), as doubles: the rotated drive of j by output
   // value (2), the rotated pairs (j, register bit 0..5) (6), the iteration's 4 thread pairs in the
@@ -205,6 +207,9 @@ hipError_t launch_real_combine(const DevProb* probs, const int2* items, int n_it
                                hipStream_t st);
 hipError_t real_occupancy(int* blocks_per_cu);
 hipError_t launch_real_init(const DevProb* probs, const int2* items, int n_items, hipStream_t st);
+// after launch_real_init, for the listed registers with a custom psi(t0) (RealTab::x0 ==
+// kRealFromBuffer): [a | b] = [Re phi0 | Im phi0] from the state buffer buf[0] (dse_init.hip)
+hipError_t launch_real_split(const DevProb* probs, const int2* items, int n_items, hipStream_t st);
 
 // Coefficient row of output j of offset set `set`: kcap1 + 1 entries, row[0].x = the degree d of
 // that output's series, row[1 + k] = a_k for k = 0..d (zero beyond): 16 B per term.
@@ -271,6 +276,11 @@ struct BasisInit {
   int64_t one_at;
 };
 hipError_t launch_basis_init(const BasisInit* list, int n_entries, uint64_t max_amps, hipStream_t st);
+// product state psi(g) = prod_b a_b[bit_b(g)] of an n-qubit register into one shard's 2^n_local
+// amplitudes (global index g = (shard << n_local) | x); amp: device, [4 n] (re a_b0, im a_b0,
+// re a_b1, im a_b1) (dse_init.hip)
+hipError_t launch_product_state(double2* out, const double* amp, int n, int n_local, uint64_t shard,
+                                hipStream_t st);
 // observables of n_out outputs of a group (grid.y): output j < n_out - 1 from intermediate
 // accumulator j, the last from state buffer role bsel; output j's partials at partial + j * out_stride
 hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,

@@ -204,9 +204,11 @@ bool nufft_grid(const double* tau, int n_t, double lam_max, NufftGrid& g) {
 
 // ---- spreading tables of one register -------------------------------------------------------
 
-// lam_lo: low parts of the eigenvalues, or null (all zero: the unrefined eigenvalues)
+// lam_lo: low parts of the eigenvalues, or null (all zero: the unrefined eigenvalues); ci: the
+// imaginary parts of the coefficients of a custom psi(t0), or null (c real: the basis state)
 void nufft_sources(const NufftGrid& g, int dim, const double* lam_hi, const double* lam_lo, const double* c,
-                   std::vector<int>& off, std::vector<int>& src, std::vector<double>& wt) {
+                   std::vector<int>& off, std::vector<int>& src, std::vector<double>& wt,
+                   const double* ci = nullptr) {
   const int M = g.M;
   const hdd two_pi_m = {kTwoPi.hi / M, 0.0};
   // 2 pi / M in double-double
@@ -229,8 +231,13 @@ void nufft_sources(const NufftGrid& g, int dim, const double* lam_hi, const doub
     const hdd phase = dd_mod2pi(dd_mul(lam, hs));  // (T/2) lambda s mod 2 pi: the centring factor
     th[a] = theta.hi + theta.lo;  // position for the window search only
     const double ph = phase.hi + phase.lo;
-    dre[a] = c[a] * std::cos(ph);
-    dim_[a] = -c[a] * std::sin(ph);
+    if (ci) {  // (c_r + i c_i) e^{-i ph}
+      dre[a] = c[a] * std::cos(ph) + ci[a] * std::sin(ph);
+      dim_[a] = ci[a] * std::cos(ph) - c[a] * std::sin(ph);
+    } else {
+      dre[a] = c[a] * std::cos(ph);
+      dim_[a] = -c[a] * std::sin(ph);
+    }
     const int mlo = (int)std::ceil((th[a] - g.alpha) / g.h), mhi = (int)std::floor((th[a] + g.alpha) / g.h);
     for (int m = mlo; m <= mhi; ++m) ++cnt[((m % M) + M) % M + 1];
   }
@@ -328,19 +335,23 @@ size_t nufft_scratch_doubles(const NufftGrid& g, int dim) {
 
 int nufft_outputs(NufftCache*& cache, hipStream_t st, const NufftGrid& g, const NufftScratch& S, const double* V,
                   const double* lam_hi, const double* lam_lo, uint64_t x0, int dim, double* Psi, int TB,
-                  const std::function<int(int tb0, int tb)>& per_block) {
+                  const std::function<int(int tb0, int tb)>& per_block, const double* c_custom) {
   // eigenvalues (refined: lam_hi + lam_lo; lam_lo null without the refinement, low parts zero and
-  // nothing read) and c = row x0 of V to the host
-  hipLaunchKernelGGL(k_nufft_row, dim3((dim + 255) / 256), dim3(256), 0, st, V, dim, x0, S.c);
-  std::vector<double> lh(dim), ll(lam_lo ? dim : 0), c(dim);
+  // nothing read) and c = row x0 of V (or the projected coefficients of a custom psi0) to the host
+  if (!c_custom) hipLaunchKernelGGL(k_nufft_row, dim3((dim + 255) / 256), dim3(256), 0, st, V, dim, x0, S.c);
+  std::vector<double> lh(dim), ll(lam_lo ? dim : 0), c(dim), ci(c_custom ? dim : 0);
+  if (c_custom && (hipMemcpyAsync(c.data(), c_custom, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                   hipMemcpyAsync(ci.data(), c_custom + dim, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess))
+    return -1;
   if (hipMemcpyAsync(lh.data(), lam_hi, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
       (lam_lo && hipMemcpyAsync(ll.data(), lam_lo, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-      hipMemcpyAsync(c.data(), S.c, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (!c_custom && hipMemcpyAsync(c.data(), S.c, dim * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess) ||
       hipStreamSynchronize(st) != hipSuccess)
     return -1;
   std::vector<int> off, src;
   std::vector<double> wt;
-  nufft_sources(g, dim, lh.data(), lam_lo ? ll.data() : nullptr, c.data(), off, src, wt);
+  nufft_sources(g, dim, lh.data(), lam_lo ? ll.data() : nullptr, c.data(), off, src, wt,
+                c_custom ? ci.data() : nullptr);
   const size_t nnz = src.size();
   if (nnz > S.nnz_cap) return -4;
   if (hipMemcpyAsync(S.off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||

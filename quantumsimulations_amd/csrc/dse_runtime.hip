@@ -95,6 +95,15 @@ struct HostProblem {
   int span_s = 0;
   // real-component mode (dse_real.hip): this evolve runs the register as two real recurrences
   bool rl = false;
+  // custom psi(t0) (ABI 14.1; every shard of a loopback register alike): 0 the basis state psi0; 1 a
+  // stored state in init_state (this shard's 2^n_local amplitudes: the one extra state-sized
+  // buffer, held only while the problem has a stored state); 2 a product state, its 4 n amplitudes
+  // in init_amp and on the device in d_init_amp.  They belong to the problem: kept over evolves and
+  // over free_device, released by dse_clear / dse_destroy or when the kind changes
+  int init_kind = 0;
+  double2* init_state = nullptr;
+  std::vector<double> init_amp;
+  double* d_init_amp = nullptr;
 };
 
 // One stream's share of the problems, grouped by tile size.
@@ -168,6 +177,7 @@ struct dse_ctx {
   std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
   bool prepared = false;
   bool evolved = false;
+  bool final_valid = false;         // the last dse_evolve returned DSE_OK (dse_continue_from_final)
   int last_q = 0;
   int tile_bits = 13;
   int n_streams = 4;
@@ -452,6 +462,13 @@ void free_wht(HostProblem& p) {
   if (p.d_cquad) (void)hipFree(p.d_cquad), p.d_cquad = nullptr;
   if (p.d_wtab) (void)hipFree(p.d_wtab), p.d_wtab = nullptr;
   p.wht_groups = 0;
+}
+
+void free_initial(HostProblem& p) {
+  if (p.init_state) (void)hipFree(p.init_state), p.init_state = nullptr;
+  if (p.d_init_amp) (void)hipFree(p.d_init_amp), p.d_init_amp = nullptr;
+  p.init_amp.clear();
+  p.init_kind = 0;
 }
 
 void free_device(dse_ctx* ctx) {
@@ -1423,6 +1440,7 @@ void dse_destroy(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
+  for (auto& p : ctx->probs) free_initial(p);
   if (ctx->d_mx) (void)hipFree(ctx->d_mx), ctx->d_mx = nullptr;
   destroy_lanes(ctx);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
@@ -1775,6 +1793,7 @@ int dse_clear(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
+  for (auto& p : ctx->probs) free_initial(p);  // the initial states go with their problems
   ctx->probs.clear();
   return DSE_OK;
 }
@@ -2108,6 +2127,7 @@ struct DenseJob {
   double *V = nullptr, *lam = nullptr, *lam_lo = nullptr, *E = nullptr, *Pm = nullptr, *Psi = nullptr, *obs = nullptr;
   double* diag_dd = nullptr;
   double* sites = nullptr;  // option site_obs: [cnt][n_t][site_stride(n)] raw site sums
+  double* c = nullptr;      // custom psi(t0): [cnt][2 dim] projected coefficients (else not allocated)
   rocblas_int* info = nullptr;
   DenseProb* d_desc = nullptr;
 };
@@ -2213,6 +2233,12 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       J->Psi = ba.get<double>(pstride * cnt);
       J->obs = ba.get<double>((size_t)n_t * 8 * cnt);
       J->sites = sS ? ba.get<double>((size_t)n_t * sS * cnt) : nullptr;
+      bool any_custom = false;
+      for (size_t i = 0; i < cnt; ++i) any_custom = any_custom || ctx->probs[J->list[i]].init_kind != 0;
+      if (any_custom && !(J->c = ba.get<double>(2 * dim * cnt))) {
+        if (!jobs.empty()) break;
+        return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
+      }
       const size_t tsz = (size_t)(2 * n * n + 5 * n);
       double* tabs = ba.get<double>(tsz * cnt);
       J->d_desc = ba.get<DenseProb>(cnt);
@@ -2237,7 +2263,11 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
         D.sea_mask = P.sea_mask;
         D.rare_bit = P.rare_bit;
         D.n_sea = __builtin_popcountll(P.sea_mask);
-        D.x0 = P.psi0;
+        D.x0 = P.init_kind ? 0 : P.psi0;  // custom psi(t0): the whole phase i^|x| is in phi0
+        if (P.init_kind) {             // (buf[0] holds psi(t0) until k_dense_final overwrites it)
+          D.init = P.buf[0];
+          D.c = J->c + 2 * dim * i;
+        }
         D.shift = P.shift;
         D.field = d;
         D.zz = d + n;
@@ -2406,6 +2436,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       const double one = 1.0, zero = 0.0;
       const auto o0 = std::chrono::steady_clock::now();
       if (ctx->dense_refine) HIPC(launch_dense_rq(desc, cnt, (int)dim, st));
+      if (J.c) HIPC(launch_dense_project(desc, cnt, (int)dim, st));  // c = V^T phi0 of the custom states
       if (use_nufft && (dim >= (size_t)kNufftMinDim || ctx->dense_nufft == 2)) {  // per register, Psi' interleaved
         for (int i = 0; i < cnt; ++i) {
           const DenseProb* di = desc + i;
@@ -2420,7 +2451,8 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
           // the low parts exist only after k_dense_rq: without the refinement none are passed (zero)
           const double* lo = ctx->dense_refine ? J.lam_lo + dim * (i0 + i) : nullptr;
           const int rc = nufft_outputs(ctx->nufft, st, ngrid, nscr, V + dim * dim * i, J.lam + dim * (i0 + i), lo,
-                                       ctx->probs[J.list[i0 + i]].psi0, (int)dim, Psi, TB, per_block);
+                                       ctx->probs[J.list[i0 + i]].psi0, (int)dim, Psi, TB, per_block,
+                                       ctx->probs[J.list[i0 + i]].init_kind ? J.c + 2 * dim * (i0 + i) : nullptr);
           if (rc) return fail(ctx, DSE_ERR_HIP, "dense engine: non-uniform FFT outputs failed (" + std::to_string(rc) + ")");
           ctx->nufft_problems++;
         }
@@ -2428,6 +2460,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       for (int tb0 = 0; tb0 < n_t; tb0 += TB) {
         const int tb = std::min(TB, n_t - tb0);
         HIPC(launch_dense_phase(desc, cnt, (int)dim, d_tau + tb0, tb, Pm, pstride, st));
+        if (J.c) HIPC(launch_dense_phase_c(desc, cnt, (int)dim, d_tau + tb0, tb, Pm, pstride, st));
         const rocblas_status rs = rocblas_dgemm_strided_batched(
             ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)dim, 2 * tb, (rocblas_int)dim, &one,
             V, (rocblas_int)dim, (rocblas_stride)(dim * dim), Pm, (rocblas_int)dim, (rocblas_stride)pstride, &zero,
@@ -2672,14 +2705,22 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
     HIPC(launch_interval(P.L, P.imag, d_p, d_items, (int)dim, 0, 0, 1, d_err, d_err, ctx->hk, st, (long)dim));
   }
   HIPC(hipEventRecord(mev[1], st));
-  // psi_0 = e_x0, psi_1 = U e_x0 (column x0), psi_{j+1} = U psi_j
-  HIPC(hipMemsetAsync(S, 0, dim * sizeof(double2), st));
-  static const double2 one_c = {1.0, 0.0};
-  HIPC(hipMemcpyAsync(S + P.psi0, &one_c, sizeof(double2), hipMemcpyHostToDevice, st));
-  if (!real_build)  // (the real build wrote column x0 itself)
-    HIPC(hipMemcpyAsync(S + dim, U + P.psi0 * dim, dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
+  // psi_0 = e_x0, psi_1 = U e_x0 (column x0), psi_{j+1} = U psi_j.  A custom psi_0 (in buf[0], written
+  // by dse_evolve's initialisation) has no column to copy: psi_1 = U psi_0 is the first product (the
+  // real build still wrote column psi0_index into psi_1's place; that product overwrites it)
+  const bool custom0 = P.init_kind != 0;
+  if (custom0) {
+    HIPC(hipMemcpyAsync(S, P.buf[0], dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
+  } else {
+    HIPC(hipMemsetAsync(S, 0, dim * sizeof(double2), st));
+    static const double2 one_c = {1.0, 0.0};
+    HIPC(hipMemcpyAsync(S + P.psi0, &one_c, sizeof(double2), hipMemcpyHostToDevice, st));
+    if (!real_build)  // (the real build wrote column x0 itself)
+      HIPC(hipMemcpyAsync(S + dim, U + P.psi0 * dim, dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
+  }
   const rocblas_double_complex one(1.0, 0.0), zero(0.0, 0.0);
-  for (int j = 1; j + 1 < n_t && real_build; ++j) {
+  const int j_first = custom0 ? 0 : 1;
+  for (int j = j_first; j + 1 < n_t && real_build; ++j) {
     if (ctx->symv_fused) {
       HIPC(launch_symv(U, (int)dim, S + dim * j, part, P.imag ? 1 : 0, st, d_cnt, S + dim * (j + 1)));
     } else {
@@ -2687,7 +2728,7 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
       HIPC(launch_symv_reduce(part, (int)dim, S + dim * (j + 1), st));
     }
   }
-  for (int j = 1; j + 1 < n_t && !real_build; ++j) {
+  for (int j = j_first; j + 1 < n_t && !real_build; ++j) {
     const rocblas_status rs = rocblas_zgemv(ctx->blas, rocblas_operation_none, (rocblas_int)dim, (rocblas_int)dim,
                                             &one, reinterpret_cast<const rocblas_double_complex*>(U),
                                             (rocblas_int)dim,
@@ -2732,7 +2773,7 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   HIPC(hipEventElapsedTime(&p_ms, mev[1], mev[2]));
   ctx->mx_build_ms = b_ms;
   ctx->mx_products_ms = p_ms;
-  ctx->mx_products = (double)std::max(0, n_t - 2);
+  ctx->mx_products = (double)std::max(0, n_t - 1 - j_first);
   ctx->mx_bytes_per_product = (double)(u_elems * sizeof(double2) + dim * sizeof(double2));
   return DSE_OK;
 }
@@ -3006,8 +3047,10 @@ int build_real_table(const HostProblem& P, RealTab& T) {
       T.rflip_mask |= 1 << (b - TB);
     }
   }
-  T.x0 = P.psi0;
-  T.x0pop = __builtin_popcountll(P.psi0);
+  // a custom psi(t0): k_real_split writes [a | b] = [Re phi0 | Im phi0] with the whole phase i^|x|
+  // in phi0, so the combine rotates back by i^{-|x|} alone
+  T.x0 = P.init_kind ? kRealFromBuffer : P.psi0;
+  T.x0pop = P.init_kind ? 0 : __builtin_popcountll(P.psi0);
   return DSE_OK;
 }
 
@@ -3763,11 +3806,16 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   hipStream_t st0 = ctx->lanes[0].stream;
   {
     std::vector<BasisInit> init;
+    std::vector<HostProblem*> custom;  // registers (shards) that start from a stored or product state
     uint64_t max_amps = 0;
     for (auto& P : ctx->probs) {
       // the re-run after a hand-off timeout keeps the dense registers' first-pass results, whose
       // final state k_dense_final wrote into buf[0]
       if (ctx->rerun && P.dn) continue;
+      if (P.init_kind) {
+        custom.push_back(&P);
+        continue;
+      }
       BasisInit e;
       e.ptr = P.buf[0];
       e.n = uint64_t(1) << P.n_local;
@@ -3795,9 +3843,21 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
       for (size_t i0 = 0; i0 < init.size(); i0 += 65535)
         HIPC(launch_basis_init(ctx->d_init + i0, (int)std::min<size_t>(65535, init.size() - i0), max_amps, st0));
     }
-    for (auto& ln : ctx->lanes)  // real-component registers: [a | b] = [e_x0 | 0]
+    // custom psi(t0) (the re-run after a hand-off timeout comes through here again: the same state)
+    for (HostProblem* P : custom) {
+      if (P->init_kind == 1)
+        HIPC(hipMemcpyAsync(P->buf[0], P->init_state, (size_t(1) << P->n_local) * sizeof(double2),
+                            hipMemcpyDeviceToDevice, st0));
+      else
+        HIPC(launch_product_state(P->buf[0], P->d_init_amp, P->n, P->n_local, (uint64_t)P->shard_rank, st0));
+    }
+    for (auto& ln : ctx->lanes)  // real-component registers: [a | b] = [e_x0 | 0], or split from buf[0]
       for (auto& g : ln.groups)
-        if (g.real) HIPC(launch_real_init(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, st0));
+        if (g.real) {
+          HIPC(launch_real_init(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, st0));
+          if (!custom.empty())
+            HIPC(launch_real_split(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, st0));
+        }
     HIPC(hipStreamSynchronize(st0));
   }
   double small_happl = 0.0, small_launches = 0.0;
@@ -4097,6 +4157,9 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     for (const auto& st : ctx->site_store) n_site += st.empty() ? 0 : 1;
     stats->site_obs_problems = n_site;
     stats->dense_output_ms = any_dense ? ctx->dense_out_ms : 0.0;
+    int n_custom = 0;  // a loopback partitioned register counts once (its shard 0)
+    for (const auto& P : ctx->probs) n_custom += (P.init_kind && (P.dist || P.shard_rank == 0)) ? 1 : 0;
+    stats->custom_init_problems = n_custom;
     stats->step_kernel_ms = launches_timed > 0 ? step_ms : -1.0;
     stats->step_launches = launches + small_launches;
     stats->timed_launches = launches_timed;
@@ -4134,10 +4197,14 @@ int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_o
   // error before any work, a failure half way): dse_get_site_obs is DSE_ERR_STATE until an evolve
   // with the option on has succeeded
   ctx->site_nt = 0;
+  ctx->final_valid = false;
   int rc = evolve_impl(ctx, t, n_t, tol, obs_out, stats);
   int* const d_err = ctx->d_err_cur;
   ctx->d_err_cur = nullptr;
-  if (rc != kRcHandoffTimeout) return rc;
+  if (rc != kRcHandoffTimeout) {
+    ctx->final_valid = rc == DSE_OK;
+    return rc;
+  }
   // A workgroup pair of a 2-tile problem was not resident together within the spin limit (the
   // device shared with long-running work of another stream or process).  The first flush after
   // the timeout saw it (launches queued behind it return at once: k_interval checks the error
@@ -4155,6 +4222,7 @@ int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_o
   ctx->d_err_cur = nullptr;
   ctx->handoff_fallbacks = 1;
   if (stats) stats->handoff_fallbacks = 1;
+  ctx->final_valid = rc == DSE_OK;
   return rc;
 }
 
@@ -4172,6 +4240,168 @@ int dse_get_state(dse_ctx* ctx, int problem, double* psi_out) {
     HostProblem& P = ctx->probs[first + i];
     const size_t amps = size_t(1) << P.n_local;
     HIPC(hipMemcpy(out + i * amps, P.buf[P.final_bsel], amps * sizeof(double2), hipMemcpyDeviceToHost));
+  }
+  return DSE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The members a custom-initial-state call on `problem` acts on (hook_members: the whole loopback
+// register for its shard 0); registers partitioned over processes are not supported.
+int init_members(dse_ctx* ctx, int problem, int* first, int* count, const char* who) {
+  const int rc = hook_members(ctx, problem, first, count);
+  if (rc) return rc;
+  if (ctx->probs[*first].dist)
+    return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over processes");
+  return DSE_OK;
+}
+
+// Every member gets its stored-state buffer (kept if it has one).  On failure the buffers this call
+// allocated are released and the members keep their previous initial state.
+int ensure_init_state(dse_ctx* ctx, int first, int count) {
+  std::vector<int> fresh;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    if (P.init_state) continue;
+    if (hipMalloc(&P.init_state, (size_t(1) << P.n_local) * sizeof(double2)) != hipSuccess) {
+      (void)hipGetLastError();
+      P.init_state = nullptr;
+      for (int j : fresh) (void)hipFree(ctx->probs[j].init_state), ctx->probs[j].init_state = nullptr;
+      return fail(ctx, DSE_ERR_OOM, "initial-state buffer allocation failed");
+    }
+    fresh.push_back(first + i);
+  }
+  return DSE_OK;
+}
+
+void set_init_stored(dse_ctx* ctx, int first, int count) {
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    if (P.d_init_amp) (void)hipFree(P.d_init_amp), P.d_init_amp = nullptr;
+    P.init_amp.clear();
+    P.init_kind = 1;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dse_set_initial_state(dse_ctx* ctx, int problem, const double* psi) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_initial_state");
+  if (rc) return rc;
+  HIPC(hipSetDevice(ctx->device));
+  if (!psi) {  // back to the basis state psi0_index
+    for (int i = 0; i < count; ++i) free_initial(ctx->probs[first + i]);
+    return DSE_OK;
+  }
+  const size_t total = size_t(1) << ctx->probs[first].n;
+  bool nonzero = false;
+  for (size_t i = 0; i < 2 * total; ++i) {
+    if (!std::isfinite(psi[i])) return fail(ctx, DSE_ERR_ARG, "dse_set_initial_state: non-finite amplitude");
+    nonzero = nonzero || psi[i] != 0.0;
+  }
+  if (!nonzero) return fail(ctx, DSE_ERR_ARG, "dse_set_initial_state: the state is zero");
+  if ((rc = ensure_init_state(ctx, first, count))) return rc;
+  const double2* in = reinterpret_cast<const double2*>(psi);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    const size_t amps = size_t(1) << P.n_local;
+    HIPC(hipMemcpy(P.init_state, in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice));
+  }
+  set_init_stored(ctx, first, count);
+  return DSE_OK;
+}
+
+int dse_set_initial_product(dse_ctx* ctx, int problem, const double* amp) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_initial_product");
+  if (rc) return rc;
+  if (!amp) return fail(ctx, DSE_ERR_ARG, "dse_set_initial_product: null amplitudes");
+  const int n = ctx->probs[first].n;
+  for (int b = 0; b < n; ++b) {
+    const double* a = amp + 4 * b;
+    if (!(std::isfinite(a[0]) && std::isfinite(a[1]) && std::isfinite(a[2]) && std::isfinite(a[3])))
+      return fail(ctx, DSE_ERR_ARG, "dse_set_initial_product: non-finite amplitude");
+    if (a[0] == 0.0 && a[1] == 0.0 && a[2] == 0.0 && a[3] == 0.0)
+      return fail(ctx, DSE_ERR_ARG, "dse_set_initial_product: amplitude pair of bit " + std::to_string(b) + " is zero");
+  }
+  HIPC(hipSetDevice(ctx->device));
+  std::vector<int> fresh;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    if (P.d_init_amp) continue;
+    if (hipMalloc(&P.d_init_amp, 4 * (size_t)n * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      P.d_init_amp = nullptr;
+      for (int j : fresh) (void)hipFree(ctx->probs[j].d_init_amp), ctx->probs[j].d_init_amp = nullptr;
+      return fail(ctx, DSE_ERR_OOM, "product-state table allocation failed");
+    }
+    fresh.push_back(first + i);
+  }
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    HIPC(hipMemcpy(P.d_init_amp, amp, 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (P.init_state) (void)hipFree(P.init_state), P.init_state = nullptr;  // no state-sized buffer is kept
+    P.init_amp.assign(amp, amp + 4 * (size_t)n);
+    P.init_kind = 2;
+  }
+  return DSE_OK;
+}
+
+int dse_continue_from_final(dse_ctx* ctx, int problem) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_continue_from_final");
+  if (rc) return rc;
+  if (!ctx->evolved || !ctx->final_valid)
+    return fail(ctx, DSE_ERR_STATE, "no final state (needs a successful dse_evolve before)");
+  HIPC(hipSetDevice(ctx->device));
+  if ((rc = ensure_init_state(ctx, first, count))) return rc;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    HIPC(hipMemcpy(P.init_state, P.buf[P.final_bsel], (size_t(1) << P.n_local) * sizeof(double2),
+                   hipMemcpyDeviceToDevice));
+  }
+  HIPC(hipDeviceSynchronize());
+  set_init_stored(ctx, first, count);
+  return DSE_OK;
+}
+
+int dse_get_initial_state(dse_ctx* ctx, int problem, double* psi_out) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_get_initial_state");
+  if (rc) return rc;
+  if (!psi_out) return fail(ctx, DSE_ERR_ARG, "null state");
+  HIPC(hipSetDevice(ctx->device));
+  double2* out = reinterpret_cast<double2*>(psi_out);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    const size_t amps = size_t(1) << P.n_local;
+    double2* dst = out + i * amps;
+    if (P.init_kind == 1) {
+      HIPC(hipMemcpy(dst, P.init_state, amps * sizeof(double2), hipMemcpyDeviceToHost));
+    } else if (P.init_kind == 2) {  // the kernel dse_evolve runs, into a buffer of the call's own
+      double2* tmp = nullptr;
+      if (hipMalloc(&tmp, amps * sizeof(double2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(ctx, DSE_ERR_OOM, "dse_get_initial_state: allocation failed");
+      }
+      hipError_t e = launch_product_state(tmp, P.d_init_amp, P.n, P.n_local, (uint64_t)P.shard_rank, nullptr);
+      if (e == hipSuccess) e = hipMemcpy(dst, tmp, amps * sizeof(double2), hipMemcpyDeviceToHost);
+      (void)hipFree(tmp);
+      HIPC(e);
+    } else {
+      std::memset(dst, 0, amps * sizeof(double2));
+      if ((P.psi0 >> P.n_local) == (uint64_t)P.shard_rank)
+        dst[P.psi0 & ((uint64_t(1) << P.n_local) - 1)] = make_double2(1.0, 0.0);
+    }
   }
   return DSE_OK;
 }

@@ -39,6 +39,7 @@ __all__ = [
     "DipolarRareParams", "get_derived_frequencies", "shell_positions_with_rare_center",
     "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch", "simulate_rare_sites",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
+    "simulate_rare_from", "simulate_rare_sequence",
 ]
 
 _ENGINES: Dict[int, object] = {}
@@ -216,3 +217,154 @@ def initial_state_rare(params: DipolarRareParams) -> np.ndarray:
     v = np.zeros(1 << prob.n_qubits, dtype=complex)
     v[prob.psi0_index] = 1.0
     return v
+
+
+# ---- evolutions from general initial states (no reference counterpart) -------------------------
+# The reference always starts from the basis ket of initial_state_rare.  The helpers below start
+# from any state of the n_sea + 1 spins: a dense ket in the reference's basis order, or a product
+# state given spin by spin.  They build the unreduced register (``reduce=False``): the frozen-rare
+# reduction of simulate_rare assumes the rare spin sits in a basis state.
+
+def reference_to_engine_state(psi_ref: np.ndarray, site_of_bit: np.ndarray) -> np.ndarray:
+    """A ket in the reference's basis order (site 0 = most significant bit) as the register state
+    whose bit b holds site ``site_of_bit[b]``.  Pure numpy."""
+    sob = np.asarray(site_of_bit, dtype=np.int64)
+    n = sob.shape[0]
+    v = np.asarray(psi_ref, dtype=np.complex128)
+    if v.shape != (1 << n,) or sorted(sob.tolist()) != list(range(n)):
+        raise ValueError(f"state must have shape ({1 << n},) and site_of_bit be a permutation of the sites")
+    # tensor axis s of the reference ket = site s; axis k of the register state = bit n - 1 - k
+    return np.ascontiguousarray(v.reshape((2,) * n).transpose([int(sob[n - 1 - k]) for k in range(n)])).reshape(-1)
+
+
+def engine_to_reference_state(psi_eng: np.ndarray, site_of_bit: np.ndarray) -> np.ndarray:
+    """Inverse of reference_to_engine_state."""
+    sob = np.asarray(site_of_bit, dtype=np.int64)
+    n = sob.shape[0]
+    v = np.asarray(psi_eng, dtype=np.complex128)
+    if v.shape != (1 << n,) or sorted(sob.tolist()) != list(range(n)):
+        raise ValueError(f"state must have shape ({1 << n},) and site_of_bit be a permutation of the sites")
+    axes = [int(sob[n - 1 - k]) for k in range(n)]  # register axis k holds site axes[k]
+    return np.ascontiguousarray(v.reshape((2,) * n).transpose(np.argsort(axes))).reshape(-1)
+
+
+def spin_amplitudes(spins, n_sites: int) -> np.ndarray:
+    """(n_sites, 2) complex amplitudes on (up, down) per site from ``spins``: either that array
+    itself, or (n_sites, 3) Bloch vectors (x, y, z) of any non-zero length, the spin pointing along
+    them: (cos(theta / 2), e^{i phi} sin(theta / 2)), so +z is up, +x is (1, 1) / sqrt(2) and +y is
+    (1, i) / sqrt(2) (<Ix>, <Iy>, <Iz> = the unit vector / 2)."""
+    a = np.asarray(spins)
+    if a.ndim != 2 or a.shape[0] != n_sites or a.shape[1] not in (2, 3):
+        raise ValueError(f"spins must have shape ({n_sites}, 2) (amplitudes) or ({n_sites}, 3) (Bloch vectors)")
+    if a.shape[1] == 2:
+        out = np.array(a, dtype=np.complex128)
+    else:
+        if np.iscomplexobj(a):
+            raise ValueError("Bloch vectors must be real")
+        r = np.array(a, dtype=np.float64)
+        if not np.all(np.isfinite(r)) or np.any(np.linalg.norm(r, axis=1) == 0.0):
+            raise ValueError("Bloch vectors must be finite and non-zero")
+        theta = np.arctan2(np.hypot(r[:, 0], r[:, 1]), r[:, 2])
+        phi = np.arctan2(r[:, 1], r[:, 0])
+        out = np.stack([np.cos(0.5 * theta).astype(np.complex128), np.exp(1j * phi) * np.sin(0.5 * theta)], axis=1)
+    if not np.all(np.isfinite(out)) or np.any(np.abs(out).max(axis=1) == 0.0):
+        raise ValueError("every spin needs a finite, non-zero amplitude pair")
+    return out
+
+
+def product_state_reference(amps: np.ndarray) -> np.ndarray:
+    """The product ket of per-site amplitudes (n_sites, 2) in the reference's basis order (the
+    Kronecker product over sites 0, 1, ...: site 0 = most significant bit)."""
+    v = np.ones(1, dtype=np.complex128)
+    for a in np.asarray(amps, dtype=np.complex128):
+        v = np.kron(v, a)
+    return v
+
+
+_SAME_SPINS = ("n_sea", "is_center_rare", "is_spin_three_half", "gamma_sea", "gamma_rare", "dipolar_scale",
+               "shell_scale")
+
+
+def _check_segments(segments) -> list:
+    segs = list(segments)
+    if not segs:
+        raise ValueError("segments must hold at least one DipolarRareParams")
+    for k, p in enumerate(segs[1:], start=1):
+        for name in _SAME_SPINS:
+            if getattr(p, name) != getattr(segs[0], name):
+                raise ValueError(f"segment {k} does not describe the same spins as segment 0: {name} differs")
+    return segs
+
+
+def _check_start(psi0, spins) -> None:
+    if (psi0 is None) == (spins is None):
+        raise ValueError("pass exactly one of psi0 and spins")
+
+
+def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site):
+    """One evolve of the unreduced register of ``params`` from an engine-order ket or a product
+    state; returns (t, obs dict, final state in engine order, the Problem)."""
+    t = time_grid(params)
+    prob = build_problem(params, order="engine", reduce=False)
+    eng.clear()
+    try:
+        pid = eng.add(prob)
+        if psi_eng is not None:
+            eng.set_initial_state(pid, psi_eng)
+        else:
+            eng.set_initial_product(pid, amps_by_site[prob.site_of_bit])
+        obs, _ = eng.evolve(t, tol=_tol())
+        final = eng.state(pid)
+    finally:
+        eng.clear()
+    return t, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}, final, prob
+
+
+def simulate_rare_from(params: DipolarRareParams, psi0=None, spins=None, return_state: bool = False,
+                       device: int | None = None):
+    """simulate_rare from a general initial state: ``(t, obs)`` as simulate_rare returns them.
+
+    Pass exactly one of ``psi0``, a dense ket of dimension 2^(n_sea + 1) in the reference's basis
+    order (what initial_state_rare and build_hamiltonian_rare use: site 0 = most significant bit),
+    and ``spins``, per-site amplitudes (n_sites, 2) on (up, down) or Bloch vectors (n_sites, 3)
+    (spin_amplitudes); a product state is built on the device.  The state need not be normalised:
+    ``obs["state_norm"]`` reports its norm, the expectations are of the normalised state.  The
+    register is built unreduced (the frozen-rare reduction assumes the basis state).
+    ``return_state=True``: ``(t, obs, psi_final)`` with the final state in the reference's order."""
+    _check_start(psi0, spins)
+    n_sites = params.n_sea + 1
+    amps = spin_amplitudes(spins, n_sites) if spins is not None else None
+    prob = build_problem(params, order="engine", reduce=False)
+    psi_eng = reference_to_engine_state(psi0, prob.site_of_bit) if psi0 is not None else None
+    eng = _engine(_default_device() if device is None else device)
+    t, obs, final, prob = _evolve_from(eng, params, psi_eng, amps)
+    if return_state:
+        return t, obs, engine_to_reference_state(final, prob.site_of_bit)
+    return t, obs
+
+
+def simulate_rare_sequence(segments, psi0=None, spins=None, device: int | None = None):
+    """A pulse sequence: piecewise-constant Hamiltonians, segment k starting from segment k - 1's
+    final state.
+
+    ``segments``: DipolarRareParams of the same spins (n_sea, geometry flags, gyromagnetic ratios
+    and couplings equal, ValueError otherwise) that differ in drives, phases, detunings and their
+    own (t_final, steps).  The start is ``psi0`` or ``spins`` as in simulate_rare_from.  Returns
+    ``([(t_0, obs_0), (t_1, obs_1), ...], psi_final)``: the times of segment k are offset by the
+    preceding segments' t_final (a junction time appears in both neighbours), psi_final is in the
+    reference's basis order.  The state is carried from one segment to the next through the host.
+    Every segment is in its own rotating frame (its omega_rf); the caller keeps them consistent."""
+    segs = _check_segments(segments)
+    _check_start(psi0, spins)
+    n_sites = segs[0].n_sea + 1
+    amps = spin_amplitudes(spins, n_sites) if spins is not None else None
+    prob0 = build_problem(segs[0], order="engine", reduce=False)
+    psi_eng = reference_to_engine_state(psi0, prob0.site_of_bit) if psi0 is not None else None
+    eng = _engine(_default_device() if device is None else device)
+    out, t_off = [], 0.0
+    for p in segs:
+        t, obs, psi_eng, prob = _evolve_from(eng, p, psi_eng, amps)
+        amps = None
+        out.append((t + t_off, obs))
+        t_off += float(p.t_final)
+    return out, engine_to_reference_state(psi_eng, prob.site_of_bit)

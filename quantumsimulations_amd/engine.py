@@ -32,11 +32,13 @@ def device_memory(device: int) -> Tuple[float, float]:
     return float(out[0]), float(out[1])
 
 
-def problem_bytes(prob: Problem) -> float:
+def problem_bytes(prob: Problem, stored_initial_state: bool = False) -> float:
     """Upper estimate of one problem's device footprint in a context: 3 state buffers, one
     intermediate output of a two-output launch, the Walsh-Hadamard engine's 2 extra vectors or the
-    2-tile hand-off ring (the larger: 2 vectors), plus tables and coefficients."""
-    return 16.0 * (3 + 1 + 2) * (1 << prob.n_qubits) + (4 << 20)
+    2-tile hand-off ring (the larger: 2 vectors), plus tables and coefficients.
+    ``stored_initial_state``: the problem will carry a stored initial state (Engine.set_initial_state
+    or continue_from_final): one more state-sized buffer (a product state costs none)."""
+    return 16.0 * (3 + 1 + 2 + (1 if stored_initial_state else 0)) * (1 << prob.n_qubits) + (4 << 20)
 
 
 # A libdse evolve runs its persistent interval kernel only when every register that is not on the
@@ -65,16 +67,17 @@ def evolve_groups(grid_keys, probs) -> Dict[Tuple, list]:
 CONTEXT_BYTES = 512 << 20
 
 
-def batches_for_memory(probs, device: int, headroom: float = 0.8):
+def batches_for_memory(probs, device: int, headroom: float = 0.8, stored_initial_state=None):
     """Index batches of ``probs`` whose summed footprint fits ``headroom`` of the free memory of
     ``device`` less one context's fixed arenas (at least one problem per batch; a problem too large
     alone still gets its own).  Call it with the context cleared, so its last batch's buffers are
-    not counted as used."""
+    not counted as used.  ``stored_initial_state``: per problem, whether it will carry a stored
+    initial state (problem_bytes); None: none does."""
     free, _ = device_memory(device)
     budget = headroom * free - CONTEXT_BYTES
     out, cur, used = [], [], 0.0
     for i, p in enumerate(probs):
-        b = problem_bytes(p)
+        b = problem_bytes(p, bool(stored_initial_state[i]) if stored_initial_state is not None else False)
         if cur and used + b > budget:
             out.append(cur)
             cur, used = [], 0.0
@@ -265,6 +268,49 @@ class Engine:
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
         self._check(self._L.dse_get_state(self._h, pid, _lib.ptr(out)))
+        return out
+
+    # -- initial states other than the basis state (include/dse.h, ABI 14.1) --
+    def _pid(self, pid: int) -> int:
+        if not 0 <= int(pid) < len(self.problems):
+            raise ValueError("bad problem id")
+        return int(pid)
+
+    def set_initial_state(self, pid: int, psi) -> None:
+        """Later evolves of register ``pid`` start from ``psi`` (2^n complex, any non-zero norm;
+        a loopback partitioned register: shard 0's id and the whole state) at t[0].  ``None``: back
+        to the basis state ``psi0_index``."""
+        pid = self._pid(pid)
+        if psi is None:
+            self._check(self._L.dse_set_initial_state(self._h, pid, None))
+            return
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        self._check(self._L.dse_set_initial_state(self._h, pid, _lib.ptr(x)))
+
+    def set_initial_product(self, pid: int, amps) -> None:
+        """Later evolves of register ``pid`` start from the product state psi(x) = prod_b
+        amps[b, bit_b(x)] (``amps``: (n, 2) complex, column 0 = bit value 0 = spin up), built on the
+        device."""
+        pid = self._pid(pid)
+        n = self.problems[pid].n_qubits
+        a = np.ascontiguousarray(amps, dtype=np.complex128)
+        if a.shape != (n, 2):
+            raise ValueError(f"amplitudes must have shape ({n}, 2)")
+        self._check(self._L.dse_set_initial_product(self._h, pid, _lib.ptr(a)))
+
+    def continue_from_final(self, pid: int) -> None:
+        """The final state of the last evolve becomes register ``pid``'s initial state (on the
+        device).  RuntimeError without a successful evolve before."""
+        self._check(self._L.dse_continue_from_final(self._h, self._pid(pid)))
+
+    def initial_state(self, pid: int) -> np.ndarray:
+        """The state the next evolve of register ``pid`` would start from."""
+        pid = self._pid(pid)
+        out = np.empty(self._dims[pid], dtype=np.complex128)
+        self._check(self._L.dse_get_initial_state(self._h, pid, _lib.ptr(out)))
         return out
 
     def energy(self, pid: int) -> Tuple[float, float]:
