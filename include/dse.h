@@ -42,7 +42,10 @@ extern "C" {
 /* Additions that leave every existing entry as it is (new functions, fields appended to dse_stats)
  * raise the minor number; a caller checks dse_abi_version() == DSE_ABI_VERSION and
  * dse_abi_minor() >= the DSE_ABI_MINOR it was built against.  14.1: initial states other than a
- * basis state (dse_set_initial_state, ...; dse_stats.custom_init_problems). */
+ * basis state (dse_set_initial_state, ...; dse_stats.custom_init_problems).
+ * Later additions leave both numbers and dse_stats alone (custom_init_problems stays its last field):
+ * a caller discovers them by name with dse_has_feature, and what would have been a stats counter is
+ * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems). */
 #define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
@@ -286,7 +289,20 @@ const char* dse_last_error(const dse_ctx* ctx);
  *                         and a second partial arena of 3 n_max + 1 doubles per tile and output
  *                         slot (capped at 256 MiB like the first).  Not available for a register
  *                         partitioned over processes (shard_rank >= 0): dse_evolve returns
- *                         DSE_ERR_ARG; any value but 0 or 1 is DSE_ERR_ARG (ABI 14) */
+ *                         DSE_ERR_ARG; any value but 0 or 1 is DSE_ERR_ARG (ABI 14)
+ *          "pair_obs"     0 (default); 1: dse_evolve also keeps, for every register and output time,
+ *                         the two-spin correlators of every pair of register bits i < j (5 sums per
+ *                         pair, see dse_pair_observables), read back with dse_get_pair_obs.  The
+ *                         aggregates and the "site_obs" traces are bitwise what they are with 0,
+ *                         and the option does not influence which engine a register runs on; with
+ *                         0 nothing is allocated and no kernel is added.  Costs one partner read per
+ *                         amplitude with bit_i = 0 and pair, and a third partial arena of
+ *                         5 n_max (n_max - 1) / 2 + 1 doubles (padded even) per tile and output
+ *                         slot.  dse_evolve returns DSE_ERR_ARG for a context holding a register
+ *                         partitioned over processes (shard_rank >= 0) and for one whose arena
+ *                         would exceed 256 MiB for a single output slot (at 2^13-amplitude tiles:
+ *                         registers above about 27 qubits); any value but 0 or 1 is DSE_ERR_ARG
+ *                         (feature "pair_obs") */
 int dse_set_option(dse_ctx* ctx, const char* key, double value);
 
 /* ---- problems ----------------------------------------------------------------------------- */
@@ -352,6 +368,21 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7);
  * kernel of the option "site_obs" whatever the option's value; a loopback partitioned register:
  * shard 0's id and the whole 2^n state; not available for a dist shard, DSE_ERR_ARG). */
 int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out);
+/* The two-spin correlators of an arbitrary state of one problem: out[5][NP], NP = n (n - 1) / 2,
+ * pair (i, j) of register bits i < j at p = j (j - 1) / 2 + i.  With s_b(x) = 1/2 - bit_b(x),
+ * y = x ^ e_i ^ e_j and every sum divided by ||psi||^2:
+ *   component 0     ZZ = <Iz_i Iz_j>  = sum_x |psi_x|^2 s_i(x) s_j(x)
+ *   components 1, 2 Re, Im of ZQ = <I+_i I-_j> = sum_{bit_i(x)=0, bit_j(x)=1} conj(psi_x) psi_y
+ *   components 3, 4 Re, Im of DQ = <I+_i I+_j> = sum_{bit_i(x)=0, bit_j(x)=0} conj(psi_x) psi_y
+ * so <IxIx> = (Re ZQ + Re DQ) / 2, <IyIy> = (Re ZQ - Re DQ) / 2, <Ix_i Iy_j> = (Im DQ - Im ZQ) / 2,
+ * <Iy_i Ix_j> = (Im DQ + Im ZQ) / 2, and with the sums of dse_site_observables
+ *   <H> = shift + sum_b field[b] Z_b + 2 sum_b (flip[4b] X_b - flip[4b+1] Y_b)
+ *         + sum_{i<j} zz[i][j] ZZ_ij + 2 sum_{i<j} pair[i][j] Re DQ_ij.
+ * The hook beside dse_site_observables: runs the kernel of the option "pair_obs" whatever the
+ * option's value; a loopback partitioned register: shard 0's id and the whole 2^n state.
+ * DSE_ERR_ARG for a context holding a register partitioned over processes, and where the option
+ * itself would be refused for the arena's size. */
+int dse_pair_observables(dse_ctx* ctx, int problem, const double* psi, double* out);
 /* Evolves every problem from its initial state at t[0] (the basis state psi0, or the state set by
  * dse_set_initial_state / dse_set_initial_product / dse_continue_from_final) through the output
  * times t[0..n_t) (strictly increasing) with an exact Chebyshev propagator (truncation tolerance
@@ -367,6 +398,19 @@ int dse_get_site_obs(dse_ctx* ctx, int problem, double* out);
 /* n_t of the results dse_get_site_obs would return (the size its caller allocates from), 0 when
  * there are none. */
 int dse_site_obs_outputs(const dse_ctx* ctx);
+/* After dse_evolve with option "pair_obs" = 1: out[5][NP][n_t], the components and pair order of
+ * dse_pair_observables at output j (a loopback partitioned register: shard 0's id, whole register;
+ * other shard ids DSE_ERR_ARG).  The lifetime rules of dse_get_site_obs: DSE_ERR_STATE before an
+ * evolve or with the option off, and after any dse_evolve that did not return DSE_OK. */
+int dse_get_pair_obs(dse_ctx* ctx, int problem, double* out);
+/* n_t of the results dse_get_pair_obs would return, 0 when there are none. */
+int dse_pair_obs_outputs(const dse_ctx* ctx);
+/* Registers whose pair sums the last successful dse_evolve produced (a loopback partitioned register
+ * counts once), 0 when there are none. */
+int dse_pair_obs_problems(const dse_ctx* ctx);
+/* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
+ * "pair_obs". */
+int dse_has_feature(const char* name);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);
 /* ---- initial states other than a basis state (ABI 14.1) --------------------------------------

@@ -32,6 +32,8 @@ EXPORTED = (
     "dse_device_memory", "dse_dist_init_exchange", "dse_site_observables", "dse_get_site_obs",
     "dse_site_obs_outputs", "dse_set_initial_state", "dse_set_initial_product",
     "dse_continue_from_final", "dse_get_initial_state", "dse_abi_minor",
+    "dse_pair_observables", "dse_get_pair_obs", "dse_pair_obs_outputs", "dse_pair_obs_problems",
+    "dse_has_feature",
 )
 DSE_DIST_ID_BYTES = 128
 DSE_XCHG_ALLTOALL, DSE_XCHG_SENDRECV, DSE_XCHG_ALLREDUCE_F64 = 1, 2, 3
@@ -114,6 +116,11 @@ def _declare(lib):
         "dse_site_observables": (C.c_int, [_vp, C.c_int, _dp, _dp]),
         "dse_get_site_obs": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_site_obs_outputs": (C.c_int, [_vp]),
+        "dse_pair_observables": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+        "dse_get_pair_obs": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_pair_obs_outputs": (C.c_int, [_vp]),
+        "dse_pair_obs_problems": (C.c_int, [_vp]),
+        "dse_has_feature": (C.c_int, [C.c_char_p]),
         "dse_set_initial_state": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_set_initial_product": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_continue_from_final": (C.c_int, [_vp, C.c_int]),
@@ -151,11 +158,19 @@ def lib():
             # a library from before 14.1 has no dse_abi_minor (nor the entries declared below)
             if not hasattr(handle, "dse_abi_minor"):
                 raise ImportError("libdse.so predates ABI 14.1; rebuild it")
+            # additions after 14.1 keep both numbers (include/dse.h): they are found by name
+            if not hasattr(handle, "dse_has_feature"):
+                raise ImportError("libdse.so predates dse_has_feature (two-spin correlators); rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
             _lib = handle
     return _lib
+
+
+def has_feature(name: str) -> bool:
+    """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs")."""
+    return bool(lib().dse_has_feature(name.encode()))
 
 
 def ptr(a):

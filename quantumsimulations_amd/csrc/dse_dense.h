@@ -47,6 +47,7 @@ struct DenseProb {
   double* obs;          // [n_t][8] raw observable sums of this problem (finish_obs order)
   double2* final_state; // [dim] psi(t_last) in the reference frame (dse_get_state), or null
   double* sites;        // option site_obs: [n_t][S] raw site sums (k_dense_obs_sites), else null
+  double* pairs;        // option pair_obs: [n_t][S] raw pair sums (k_dense_obs_pairs), else null
   // custom psi(t0) (ABI 14.1): init = psi0 in the reference frame (dim amplitudes, read before the
   // final state is written: it may alias final_state), c = [Re c | Im c] (2 dim) of c = V^T phi0,
   // phi0_x = i^|x| psi0_x (rot) written by launch_dense_project; x0 is then 0.  Both null: psi(t0) =
@@ -86,6 +87,13 @@ hipError_t launch_state_obs(const DenseProb* d, int dim, const double2* states, 
 hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
                                   int tb, int t0, int S, hipStream_t st);
 hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                    hipStream_t st);
+// option pair_obs (dse_pairs.hip): the two-spin sums of the same columns into d[p].pairs rows t0 ..
+// t0 + tb of S >= pair_stride(n) doubles (ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at [5 p + c],
+// ||psi||^2 at [5 NP]); _c as above
+hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                  int tb, int t0, int S, hipStream_t st);
+hipError_t launch_dense_obs_pairs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
                                     hipStream_t st);
 // psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
 // the shift's phase exp(-i shift tau_last) included)

@@ -30,6 +30,10 @@ constexpr int kMaxQubits = 34;                    // DSE_MAX_QUBITS
 // Site-resolved observables: sums per register and state, X_b Y_b Z_b at [3 b + c] for b < n and
 // ||psi||^2 at [3 n], padded to an even count (16-byte records)
 __host__ __device__ constexpr int site_stride(int n) { return (3 * n + 2) & ~1; }
+// Two-spin correlators: sums per register and state, ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of the pair
+// (i, j), i < j, at [5 pair_index(i, j) + c] and ||psi||^2 at [5 NP], NP = n (n - 1) / 2, padded even
+__host__ __device__ constexpr int pair_index(int i, int j) { return j * (j - 1) / 2 + i; }
+__host__ __device__ constexpr int pair_stride(int n) { return (5 * (n * (n - 1) / 2) + 2) & ~1; }
 constexpr int kMaxShardBits = 3;                  // partitioned registers: up to 8 shards
 constexpr int kMaxShards = 1 << kMaxShardBits;
 // bits above an L-bit tile for the largest register (34 qubits), at least the 32-bit tile index
@@ -289,6 +293,11 @@ hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_item
 // site-resolved sums of the same outputs (k_obs_sites): S >= site_stride(n) doubles per tile, output
 // j's partials at partial + j * out_stride
 hipError_t launch_obs_sites(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                            double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
+                            int xq = 0);
+// the two-spin sums of the same outputs (k_obs_pairs, dse_pairs.hip): S >= pair_stride(n) doubles per
+// tile, output j's partials at partial + j * out_stride
+hipError_t launch_obs_pairs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                             double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                             int xq = 0);
 // partial[2 * block + {0, 1}] = block sums of Re(conj(a) b) and |a|^2 over n amplitudes

@@ -174,6 +174,18 @@ struct dse_ctx {
   int site_nt = 0;                  // output times of site_store (0: none)
   double* d_small_sites = nullptr;  // small engine: [problem][n_t][kSmallSiteStride] raw site sums
   size_t small_sites_cap = 0;
+  // two-spin correlators (option "pair_obs", dse_pair_observables): a third partial arena for
+  // k_obs_pairs, pair_S doubles per tile and slot (pair_stride of the context's widest register),
+  // and the results of the last evolve, per register [5][NP][n_t] (loopback group: shard 0's entry)
+  int pair_obs = 0;
+  double* d_pair_partial = nullptr;
+  size_t pair_slots = 0;
+  int pair_S = 0;
+  std::vector<std::vector<double>> pair_store;
+  int pair_nt = 0;                  // output times of pair_store (0: none)
+  int pair_problems = 0;            // registers with pair sums in the last successful evolve
+  double* d_small_pairs = nullptr;  // small engine: [problem][n_t][kSmallPairStride] raw pair sums
+  size_t small_pairs_cap = 0;
   std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
   bool prepared = false;
   bool evolved = false;
@@ -496,6 +508,13 @@ void free_device(dse_ctx* ctx) {
   ctx->small_sites_cap = 0;
   ctx->site_store.clear();
   ctx->site_nt = 0;
+  if (ctx->d_pair_partial) (void)hipFree(ctx->d_pair_partial), ctx->d_pair_partial = nullptr;
+  ctx->pair_slots = 0;
+  if (ctx->d_small_pairs) (void)hipFree(ctx->d_small_pairs), ctx->d_small_pairs = nullptr;
+  ctx->small_pairs_cap = 0;
+  ctx->pair_store.clear();
+  ctx->pair_nt = 0;
+  ctx->pair_problems = 0;
   for (auto& kv : ctx->zzlo_tables) (void)hipFree(kv.second);
   if (ctx->d_flags) (void)hipFree(ctx->d_flags), ctx->d_flags = nullptr;
   ctx->flags_cap = 0;
@@ -1243,6 +1262,98 @@ void reset_site_store(dse_ctx* ctx, int n_t) {
   }
 }
 
+// ---- two-spin correlators (option pair_obs): the third arena and its host store ---------------
+
+constexpr int64_t kPartialCapBytes = 256ll << 20;  // one output slot of a partial arena
+
+int pair_n_max(const dse_ctx* ctx) {
+  int n_max = 1;
+  for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
+  return n_max;
+}
+
+// Refusals of the option and of the hook, decided before any work (after prepare: the tile count is
+// known): no register partitioned over processes, and one output slot of the arena, tiles x
+// pair_stride(n_max) doubles, within the cap of the other arenas
+int pair_refusal(dse_ctx* ctx, const char* who) {
+  for (const auto& P : ctx->probs)
+    if (P.dist)
+      return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over "
+                                        "processes (the all-reduce of the pair sums is not implemented)");
+  const int64_t per_slot = ctx->total_items * (int64_t)pair_stride(pair_n_max(ctx)) * 8;
+  if (per_slot > kPartialCapBytes)
+    return fail(ctx, DSE_ERR_ARG, std::string(who) + ": the pair sums of one output (" + std::to_string(ctx->total_items) +
+                                      " tiles x " + std::to_string(pair_stride(pair_n_max(ctx))) +
+                                      " doubles) exceed the 256 MiB partial arena");
+  return DSE_OK;
+}
+
+// slots x total_items x S doubles, S = pair_stride of the widest register of the context
+int ensure_pair_partial(dse_ctx* ctx, size_t slots) {
+  const int S = pair_stride(pair_n_max(ctx));
+  if (ctx->pair_slots >= slots && ctx->pair_S == S) return DSE_OK;
+  if (ctx->d_pair_partial) (void)hipFree(ctx->d_pair_partial), ctx->d_pair_partial = nullptr;
+  ctx->pair_slots = 0;
+  if (hipMalloc(&ctx->d_pair_partial, slots * std::max<int64_t>(1, ctx->total_items) * S * sizeof(double)) != hipSuccess)
+    return fail(ctx, DSE_ERR_OOM, "device allocation of pair-observable partials failed");
+  ctx->pair_slots = slots;
+  ctx->pair_S = S;
+  return DSE_OK;
+}
+
+// raw pair sums v (ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at [5 p + c], ||psi||^2 at [5 NP]) of an
+// n-qubit register, normalised into o[c][p] at o[(c * NP + p) * stride]
+void finish_pairs(int n, const double* v, double* o, size_t stride) {
+  const int np = n * (n - 1) / 2;
+  const double n2 = v[5 * np];
+  const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
+  for (int p = 0; p < np; ++p)
+    for (int c = 0; c < 5; ++c) o[((size_t)c * np + p) * stride] = v[5 * p + c] * inv;
+}
+
+size_t pair_store_size(const HostProblem& P, int n_t) { return (size_t)5 * (P.n * (P.n - 1) / 2) * n_t; }
+// which registers keep a record (a loopback group's sums live in shard 0's entry)
+bool pair_record(const dse_ctx* ctx, const HostProblem& P) {
+  return ctx->pair_obs && !(P.shard_bits > 0 && P.shard_rank != 0);
+}
+
+// A fresh store for this evolve, under reset_site_store's rules (the re-run after a hand-off
+// timeout starts over, except for the dense registers' first-pass results)
+void reset_pair_store(dse_ctx* ctx, int n_t) {
+  ctx->pair_store.resize(ctx->probs.size());
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    std::vector<double>& st = ctx->pair_store[pi];
+    const size_t want = pair_record(ctx, P) ? pair_store_size(P, n_t) : 0;
+    if (ctx->rerun && P.dn && pair_record(ctx, P) && st.size() == want) continue;
+    st.assign(want, 0.0);
+  }
+}
+
+// the pair half of flush_partials: tiles in order, a loopback group's members into shard 0's record
+int flush_pair_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t) {
+  const size_t S = (size_t)ctx->pair_S;
+  std::vector<double> hs(nslots * ctx->total_items * S);
+  HIPC(hipMemcpy(hs.data(), ctx->d_pair_partial, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  std::vector<double> v(S);
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    if (P.side() || !pair_record(ctx, P)) continue;
+    const size_t n_members = P.shard_bits > 0 ? (size_t(1) << P.shard_bits) : 1;
+    const int nv = 5 * (P.n * (P.n - 1) / 2);
+    for (size_t s = 0; s < nslots; ++s) {
+      std::fill(v.begin(), v.end(), 0.0);
+      for (size_t mi = pi; mi < pi + n_members; ++mi) {
+        const double* row = hs.data() + (s * ctx->total_items + ctx->item_pos[mi]) * S;
+        for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t)
+          for (int j = 0; j <= nv; ++j) v[j] += row[t * S + j];
+      }
+      finish_pairs(P.n, v.data(), ctx->pair_store[pi].data() + (t0 + s), (size_t)n_t);
+    }
+  }
+  return DSE_OK;
+}
+
 void finish_obs(const HostProblem& P, const double* v, double* o, size_t stride) {
   const double n2 = v[6];
   const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
@@ -1288,6 +1399,10 @@ int flush_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t, double* obs_
         finish_obs(P, v, obs_out + pi * DSE_N_OBS * (size_t)n_t + (t0 + s), (size_t)n_t);
       }
     }
+  }
+  if (ctx->pair_obs) {
+    const int prc = flush_pair_partials(ctx, nslots, t0, n_t);
+    if (prc) return prc;
   }
   if (!ctx->site_obs) return DSE_OK;
   // the site sums of the same slots: tiles in order, a loopback group's members into shard 0's record
@@ -1469,6 +1584,9 @@ int dse_set_option(dse_ctx* ctx, const char* key, double value) {
   } else if (k == "site_obs") {  // site-resolved observables beside the seven aggregates
     if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "site_obs must be 0 or 1");
     ctx->site_obs = (int)value;
+  } else if (k == "pair_obs") {  // two-spin correlators of every pair of register bits
+    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "pair_obs must be 0 or 1");
+    ctx->pair_obs = (int)value;
   } else if (k == "persistent") {
     ctx->persistent = value != 0.0;
   } else if (k == "swap_overlap") {
@@ -1983,6 +2101,17 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     }
   }
   double* const d_sites = ctx->site_obs ? ctx->d_small_sites : nullptr;
+  if (ctx->pair_obs) {
+    const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallPairStride;
+    if (sn > ctx->small_pairs_cap) {
+      if (ctx->d_small_pairs) (void)hipFree(ctx->d_small_pairs), ctx->d_small_pairs = nullptr;
+      ctx->small_pairs_cap = 0;
+      if (hipMalloc(&ctx->d_small_pairs, sn * sizeof(double)) != hipSuccess)
+        return fail(ctx, DSE_ERR_OOM, "small-engine pair output allocation failed");
+      ctx->small_pairs_cap = sn;
+    }
+  }
+  double* const d_pairs = ctx->pair_obs ? ctx->d_small_pairs : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
   if (outn > ctx->small_out_cap) {
     if (ctx->d_small_out) (void)hipFree(ctx->d_small_out), ctx->d_small_out = nullptr;
@@ -2004,13 +2133,13 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second,
-                           ctx->d_small_out, st, d_sites));
+                           ctx->d_small_out, st, d_sites, d_pairs));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux + iv_off, ctx->d_small_out, st, d_sites));
+                        cnt, ctx->d_small_aux + iv_off, ctx->d_small_out, st, d_sites, d_pairs));
       *launches += 1.0;
     }
   }
@@ -2030,6 +2159,17 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
     for (int ti = 0; ti < n_t; ++ti)
       finish_obs(P, h.data() + (pi * (size_t)n_t + ti) * 8, obs_out + pi * DSE_N_OBS * (size_t)n_t + ti,
                  (size_t)n_t);
+  }
+  if (ctx->pair_obs) {
+    std::vector<double> hp(ctx->probs.size() * (size_t)n_t * kSmallPairStride);
+    HIPC(hipMemcpy(hp.data(), ctx->d_small_pairs, hp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+      const HostProblem& P = ctx->probs[pi];
+      if (!P.sm) continue;
+      for (int ti = 0; ti < n_t; ++ti)
+        finish_pairs(P.n, hp.data() + (pi * (size_t)n_t + ti) * kSmallPairStride, ctx->pair_store[pi].data() + ti,
+                     (size_t)n_t);
+    }
   }
   if (!ctx->site_obs) return DSE_OK;
   std::vector<double> hs(ctx->probs.size() * (size_t)n_t * kSmallSiteStride);
@@ -2127,6 +2267,7 @@ struct DenseJob {
   double *V = nullptr, *lam = nullptr, *lam_lo = nullptr, *E = nullptr, *Pm = nullptr, *Psi = nullptr, *obs = nullptr;
   double* diag_dd = nullptr;
   double* sites = nullptr;  // option site_obs: [cnt][n_t][site_stride(n)] raw site sums
+  double* pairs = nullptr;  // option pair_obs: [cnt][n_t][pair_stride(n)] raw pair sums
   double* c = nullptr;      // custom psi(t0): [cnt][2 dim] projected coefficients (else not allocated)
   rocblas_int* info = nullptr;
   DenseProb* d_desc = nullptr;
@@ -2213,7 +2354,8 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       const int TB = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_t, (size_t(256) << 20) / (16 * dim)));
       const size_t pstride = dim * 2 * (size_t)TB;
       const size_t sS = ctx->site_obs ? (size_t)site_stride(n) : 0;  // site sums per output
-      const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + sS) + 2 * n * n + 4 * n) * sizeof(double));
+      const size_t pS = ctx->pair_obs ? (size_t)pair_stride(n) : 0;  // pair sums per output
+      const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + sS + pS) + 2 * n * n + 4 * n) * sizeof(double));
       size_t same = 0;
       while (idx + same < order.size() && ctx->probs[order[idx + same]].n_local == n) ++same;
       size_t cnt = (size_t)std::max(0.0, (budget - used) / per);
@@ -2233,6 +2375,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       J->Psi = ba.get<double>(pstride * cnt);
       J->obs = ba.get<double>((size_t)n_t * 8 * cnt);
       J->sites = sS ? ba.get<double>((size_t)n_t * sS * cnt) : nullptr;
+      J->pairs = pS ? ba.get<double>((size_t)n_t * pS * cnt) : nullptr;
       bool any_custom = false;
       for (size_t i = 0; i < cnt; ++i) any_custom = any_custom || ctx->probs[J->list[i]].init_kind != 0;
       if (any_custom && !(J->c = ba.get<double>(2 * dim * cnt))) {
@@ -2243,7 +2386,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
       double* tabs = ba.get<double>(tsz * cnt);
       J->d_desc = ba.get<DenseProb>(cnt);
       if (!J->V || !J->lam || !J->lam_lo || !J->diag_dd || !J->E || !J->info || !J->Pm || !J->Psi || !J->obs || !tabs || !J->d_desc ||
-          (sS && !J->sites)) {
+          (sS && !J->sites) || (pS && !J->pairs)) {
         if (!jobs.empty()) break;  // this round is full: the register waits for the next one
         return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
       }
@@ -2281,6 +2424,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
         D.obs = J->obs + (size_t)n_t * 8 * i;
         D.final_state = P.buf[0];
         D.sites = sS ? J->sites + (size_t)n_t * sS * i : nullptr;
+        D.pairs = pS ? J->pairs + (size_t)n_t * pS * i : nullptr;
       }
       HIPC(hipMemcpyAsync(tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
       HIPC(hipMemcpyAsync(J->d_desc, desc.data(), desc.size() * sizeof(DenseProb), hipMemcpyHostToDevice, st));
@@ -2444,6 +2588,8 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
             if (launch_dense_obs_c(di, (int)dim, Psi, tb, tb0, st) != hipSuccess) return -1;
             if (J.sites && launch_dense_obs_sites_c(di, (int)dim, Psi, tb, tb0, site_stride(J.n), st) != hipSuccess)
               return -1;
+            if (J.pairs && launch_dense_obs_pairs_c(di, (int)dim, Psi, tb, tb0, pair_stride(J.n), st) != hipSuccess)
+              return -1;
             if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, Psi, tb, tau[n_t - 1], st) != hipSuccess)
               return -1;
             return 0;
@@ -2469,6 +2615,7 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
           return fail(ctx, DSE_ERR_HIP, "rocblas dgemm failed (status " + std::to_string((int)rs) + ")");
         HIPC(launch_dense_obs(desc, cnt, (int)dim, Psi, pstride, tb, tb0, st));
         if (J.sites) HIPC(launch_dense_obs_sites(desc, cnt, (int)dim, Psi, pstride, tb, tb0, site_stride(J.n), st));
+        if (J.pairs) HIPC(launch_dense_obs_pairs(desc, cnt, (int)dim, Psi, pstride, tb, tb0, pair_stride(J.n), st));
         if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, Psi, pstride, tb, tau[n_t - 1], st));
       }
       std::vector<double> h((size_t)n_t * 8 * cnt);
@@ -2478,7 +2625,16 @@ int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* m
         hs.resize((size_t)n_t * site_stride(J.n) * cnt);
         HIPC(hipMemcpyAsync(hs.data(), J.sites, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
       }
+      std::vector<double> hpr;
+      if (J.pairs) {
+        hpr.resize((size_t)n_t * pair_stride(J.n) * cnt);
+        HIPC(hipMemcpyAsync(hpr.data(), J.pairs, hpr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      }
       HIPC(hipStreamSynchronize(st));
+      for (int i = 0; i < cnt && J.pairs; ++i)
+        for (int ti = 0; ti < n_t; ++ti)
+          finish_pairs(J.n, hpr.data() + ((size_t)i * n_t + ti) * pair_stride(J.n),
+                       ctx->pair_store[J.list[i]].data() + ti, (size_t)n_t);
       for (int i = 0; i < cnt && J.sites; ++i)
         for (int ti = 0; ti < n_t; ++ti)
           finish_sites(J.n, hs.data() + ((size_t)i * n_t + ti) * site_stride(J.n),
@@ -2633,6 +2789,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   // last and only with the option on: every other offset, and mx_cap with it off, as before)
   const int sS = site_stride(n);
   const size_t oSites = ctx->site_obs ? take((size_t)n_t * sS * sizeof(double)) : 0;
+  const int pS = pair_stride(n);  // option pair_obs: likewise
+  const size_t oPairs = ctx->pair_obs ? take((size_t)n_t * pS * sizeof(double)) : 0;
   if (off > ctx->mx_cap) {
     if (ctx->d_mx) (void)hipFree(ctx->d_mx), ctx->d_mx = nullptr;
     ctx->mx_cap = 0;
@@ -2747,6 +2905,7 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.x0 = P.psi0;
   D.obs = d_obs;
   if (ctx->site_obs) D.sites = reinterpret_cast<double*>(base + oSites);
+  if (ctx->pair_obs) D.pairs = reinterpret_cast<double*>(base + oPairs);
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
   std::vector<double> hsites;
@@ -2754,6 +2913,12 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
     hsites.resize((size_t)n_t * sS);
     HIPC(launch_dense_obs_sites_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, sS, st));
     HIPC(hipMemcpyAsync(hsites.data(), D.sites, hsites.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  std::vector<double> hpairs;
+  if (D.pairs) {
+    hpairs.resize((size_t)n_t * pS);
+    HIPC(launch_dense_obs_pairs_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, pS, st));
+    HIPC(hipMemcpyAsync(hpairs.data(), D.pairs, hpairs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPC(hipMemcpyAsync(P.buf[0], S + dim * (size_t)(n_t - 1), dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
   std::vector<double> h((size_t)n_t * 8);
@@ -2766,6 +2931,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
     finish_obs(P, h.data() + (size_t)ti * 8, obs_out + (size_t)pi * DSE_N_OBS * n_t + ti, (size_t)n_t);
   for (int ti = 0; ti < n_t && D.sites; ++ti)
     finish_sites(n, hsites.data() + (size_t)ti * sS, ctx->site_store[pi].data() + ti, (size_t)n_t);
+  for (int ti = 0; ti < n_t && D.pairs; ++ti)
+    finish_pairs(n, hpairs.data() + (size_t)ti * pS, ctx->pair_store[pi].data() + ti, (size_t)n_t);
   P.degree = deg;
   *h_apps = (double)deg * (double)dim;
   float b_ms = 0.f, p_ms = 0.f;
@@ -2899,6 +3066,69 @@ int dse_get_site_obs(dse_ctx* ctx, int problem, double* out) {
     return fail(ctx, DSE_ERR_STATE, "no site observables (set option site_obs = 1 and call dse_evolve first)");
   std::copy(ctx->site_store[problem].begin(), ctx->site_store[problem].end(), out);
   return DSE_OK;
+}
+
+int dse_pair_observables(dse_ctx* ctx, int problem, const double* psi, double* out) {
+  if (!ctx) return DSE_ERR_ARG;
+  if (!psi || !out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  HIPC(hipSetDevice(ctx->device));
+  if ((rc = prepare(ctx))) return rc;
+  if ((rc = pair_refusal(ctx, "dse_pair_observables"))) return rc;
+  int64_t tiles = 0;
+  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
+  if ((rc = ensure_pair_partial(ctx, 1))) return rc;
+  const size_t S = (size_t)ctx->pair_S;
+  hipStream_t st = ctx->lanes[0].stream;
+  const double2* in = reinterpret_cast<const double2*>(psi);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    const size_t amps = size_t(1) << P.n_local;
+    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
+  }
+  int64_t off = 0;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    HIPC(launch_obs_pairs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_pair_partial + off * S,
+                          (int)S, st));
+    off += P.n_tiles;
+  }
+  std::vector<double> h(tiles * S);
+  HIPC(hipMemcpyAsync(h.data(), ctx->d_pair_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const int n = ctx->probs[first].n;
+  const int nv = 5 * (n * (n - 1) / 2);
+  std::vector<double> v(S, 0.0);
+  for (int64_t t = 0; t < tiles; ++t)
+    for (int j = 0; j <= nv; ++j) v[j] += h[t * S + j];
+  finish_pairs(n, v.data(), out, 1);
+  ctx->evolved = false;
+  return DSE_OK;
+}
+
+int dse_pair_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->pair_nt : DSE_ERR_ARG; }
+
+int dse_pair_obs_problems(const dse_ctx* ctx) { return ctx ? (ctx->pair_nt > 0 ? ctx->pair_problems : 0) : DSE_ERR_ARG; }
+
+int dse_get_pair_obs(dse_ctx* ctx, int problem, double* out) {
+  if (!ctx) return DSE_ERR_ARG;
+  if (!out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  if (ctx->pair_nt <= 0 || (size_t)problem >= ctx->pair_store.size() || !pair_record(ctx, ctx->probs[problem]) ||
+      ctx->pair_store[problem].size() != pair_store_size(ctx->probs[problem], ctx->pair_nt))
+    return fail(ctx, DSE_ERR_STATE, "no pair observables (set option pair_obs = 1 and call dse_evolve first)");
+  std::copy(ctx->pair_store[problem].begin(), ctx->pair_store[problem].end(), out);
+  return DSE_OK;
+}
+
+int dse_has_feature(const char* name) {
+  if (!name) return 0;
+  const std::string k(name);
+  return k == "site_obs" || k == "initial_state" || k == "pair_obs";
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -3128,7 +3358,9 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
       if (P.dist)
         return fail(ctx, DSE_ERR_ARG, "site_obs: not available for a register partitioned over processes "
                                       "(the all-reduce of the site sums is not implemented)");
+  if (ctx->pair_obs && (rc = pair_refusal(ctx, "pair_obs"))) return rc;
   reset_site_store(ctx, n_t);
+  reset_pair_store(ctx, n_t);
   bool persistent = ctx->persistent != 0;
   bool any_dist = false;
   // spanning registers (options span / span_tile): every register that fits runs on k_span over
@@ -3878,9 +4110,15 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     const int64_t per_slot = ctx->total_items * (int64_t)site_stride(n_max) * 8;
     chunk = std::min(chunk, (size_t)std::max<int64_t>(M, std::min<int64_t>(
                                 n_t, std::max<int64_t>(1, (int64_t)(256ll << 20) / per_slot))));
-    if ((rc = ensure_site_partial(ctx, chunk))) return rc;
   }
-  const bool sites_on = ctx->site_obs != 0;
+  if (ctx->pair_obs) {  // the third arena likewise (one slot fits the cap: pair_refusal)
+    const int64_t per_slot = std::max<int64_t>(1, ctx->total_items) * (int64_t)pair_stride(pair_n_max(ctx)) * 8;
+    chunk = std::min(chunk, (size_t)std::max<int64_t>(M, std::min<int64_t>(
+                                n_t, std::max<int64_t>(1, kPartialCapBytes / per_slot))));
+  }
+  if (ctx->site_obs && (rc = ensure_site_partial(ctx, chunk))) return rc;
+  if (ctx->pair_obs && (rc = ensure_pair_partial(ctx, chunk))) return rc;
+  const bool sites_on = ctx->site_obs != 0, pairs_on = ctx->pair_obs != 0;
   if ((rc = ensure_partial(ctx, chunk))) return rc;
   if (ctx->time_every > 0)
     for (auto& ln : ctx->lanes) {
@@ -3939,6 +4177,10 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
           HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
                                 ctx->d_site_partial + (slot * ctx->total_items + g.off) * ctx->site_S,
                                 ctx->site_S, os, n_out, (size_t)ctx->total_items * ctx->site_S, xq));
+        if (pairs_on)
+          HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
+                                ctx->d_pair_partial + (slot * ctx->total_items + g.off) * ctx->pair_S,
+                                ctx->pair_S, os, n_out, (size_t)ctx->total_items * ctx->pair_S, xq));
       }
       if (obs_ovl) {
         HIPC(hipEventRecord(ln.ev_obs[xq], os));
@@ -4085,6 +4327,11 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
                                     j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
                                     ctx->d_site_partial + ((slot + j) * ctx->total_items + g.off) * ctx->site_S,
                                     ctx->site_S, ln.stream, 1, 0, q));
+            if (pairs_on)
+              HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
+                                    j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
+                                    ctx->d_pair_partial + ((slot + j) * ctx->total_items + g.off) * ctx->pair_S,
+                                    ctx->pair_S, ln.stream, 1, 0, q));
           }
       }
     } else if ((rc = obs_all(q ? 0 : 2, slot, G.n_out, q))) {
@@ -4127,6 +4374,11 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
   ctx->evolved = true;
   if (ctx->site_obs) ctx->site_nt = n_t;  // the store is complete: dse_get_site_obs may read it
+  if (ctx->pair_obs) {
+    ctx->pair_nt = n_t;
+    ctx->pair_problems = 0;
+    for (const auto& P : ctx->probs) ctx->pair_problems += pair_record(ctx, P) ? 1 : 0;
+  }
 
   if (stats) {
     double happl = small_happl + matrix_happl;
@@ -4197,6 +4449,7 @@ int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_o
   // error before any work, a failure half way): dse_get_site_obs is DSE_ERR_STATE until an evolve
   // with the option on has succeeded
   ctx->site_nt = 0;
+  ctx->pair_nt = 0;  // (the pair observables likewise)
   ctx->final_valid = false;
   int rc = evolve_impl(ctx, t, n_t, tol, obs_out, stats);
   int* const d_err = ctx->d_err_cur;

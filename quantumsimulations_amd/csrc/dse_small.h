@@ -12,6 +12,9 @@ constexpr int kSmallMaxQubits = 9;
 // site-resolved sums per problem and output (option site_obs): X_b Y_b Z_b at [3 b + c], ||psi||^2
 // at [3 n], padded to an even count for n = 9
 constexpr int kSmallSiteStride = 28;
+// two-spin sums per problem and output (option pair_obs): ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at
+// [5 p + c], ||psi||^2 at [5 NP], padded to an even count for n = 9 (pair_stride(9))
+constexpr int kSmallPairStride = 182;
 
 struct SmallProb {
   double2* state;          // [2^n] the state at the start of the next launch
@@ -29,10 +32,12 @@ struct SmallProb {
 // One launch: intervals m0 .. m0 + n_int - 1 of problems sel[0 .. count) (all with n qubits);
 // out[problem][m + 1][8] = raw observable sums of psi(t_{m+1}) (dse_runtime.hip finish_obs).
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
-                        const int* iv_set, double* out, hipStream_t st, double* sites = nullptr);
+                        const int* iv_set, double* out, hipStream_t st, double* sites = nullptr,
+                        double* pairs = nullptr);
 // out[problem][0][8] = observable sums of the state buffer (psi0)
 // sites non-null (both launches): also sites[problem][m][kSmallSiteStride], the site-resolved sums
+// pairs non-null (both launches): also pairs[problem][m][kSmallPairStride], the two-spin sums
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites = nullptr);
+                             hipStream_t st, double* sites = nullptr, double* pairs = nullptr);
 
 }  // namespace dse

@@ -73,12 +73,59 @@ __device__ __forceinline__ void small_site_sums(const double2* w, int lane, bool
   }
 }
 
+// Two-spin sums of the state in LDS w (option pair_obs; the record of dse_pairs.hip): for every pair
+// i < j the amplitudes with bit_i = 0 read their partner x ^ e_i ^ e_j, bit_j sends the product to ZQ
+// or DQ; each sum one wave butterfly, pairs in index order.
+template <int N>
+__device__ __forceinline__ void small_pair_sums(const double2* w, int lane, bool live, double* o) {
+  constexpr int R = SmallGeo<N>::R, NP = SmallGeo<N>::NP;
+  double n2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double2 p = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
+    n2 += p.x * p.x + p.y * p.y;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+  if (lane == 0) o[5 * NP] = n2;
+  for (int i = 5 * NP + 1 + lane; i < kSmallPairStride; i += 64) o[i] = 0.0;
+  int e = 0;
+  for (int j = 1; j < N; ++j)
+    for (int i = 0; i < j; ++i, ++e) {
+      double v[5] = {0, 0, 0, 0, 0};
+      const int m = (1 << i) | (1 << j);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int x = r * 64 + lane;
+        if (!live) continue;
+        const double2 p = w[x];
+        const double p2 = p.x * p.x + p.y * p.y;
+        const bool i1 = (x >> i) & 1, j1 = (x >> j) & 1;
+        v[0] += (i1 != j1 ? -0.25 : 0.25) * p2;
+        if (i1) continue;
+        const double2 s = w[x ^ m];
+        const double re = p.x * s.x + p.y * s.y, im = p.x * s.y - p.y * s.x;
+        if (j1)
+          v[1] += re, v[2] += im;
+        else
+          v[3] += re, v[4] += im;
+      }
+#pragma unroll
+      for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+      if (lane < 5) o[5 * e + lane] = lane == 0 ? v[0] : lane == 1 ? v[1] : lane == 2 ? v[2] : lane == 3 ? v[3] : v[4];
+    }
+}
+
 // SITES: also the site-resolved sums of every output into sites[problem][m][kSmallSiteStride]
-// (the 7 aggregate sums keep their code and order)
-template <int N, bool SITES>
+// (the 7 aggregate sums keep their code and order); PAIRS: after them the two-spin sums into
+// pairs[problem][m][kSmallPairStride]
+template <int N, bool SITES, bool PAIRS>
 __global__ void __launch_bounds__(64)
 k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0, int n_int,
-        const int* __restrict__ iv_set, double* __restrict__ out, double* __restrict__ sites) {
+        const int* __restrict__ iv_set, double* __restrict__ out, double* __restrict__ sites,
+        double* __restrict__ pairs) {
   using G = SmallGeo<N>;
   constexpr int R = G::R, DIM = G::DIM, NP = G::NP;
   __shared__ double2 w[DIM];
@@ -114,7 +161,15 @@ k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0
       for (int c = b + 1; c < N; ++c) d += P.zz[b * N + c] * (sb * (0.5 - (double)((x >> c) & 1)));
     }
     dmb[r] = d;
-    if (live) w[x] = gld(gst_, x);
+    if (!PAIRS && live) w[x] = gld(gst_, x);  // (the instances without pair sums: their code as it was)
+  }
+  if (PAIRS) {
+    // The state in a loop of its own.  Stored to LDS inside the loop above, each store might alias the
+    // coefficient tables read through generic pointers, so all R x N (N + 1) / 2 loads are issued again
+    // per row: at N = 9 that prologue spilled (246 VGPRs, 988 B of scratch per lane).
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (live) w[r * 64 + lane] = gld(gst_, r * 64 + lane);
   }
   __syncthreads();
 
@@ -240,6 +295,8 @@ k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0
     if (lane < 8) out[((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * 8 + lane] = lane < 7 ? red[lane] : 0.0;
     if (SITES)
       small_site_sums<N>(w, lane, live, sites + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallSiteStride);
+    if (PAIRS)
+      small_pair_sums<N>(w, lane, live, pairs + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallPairStride);
     __syncthreads();
   }
 #pragma unroll
@@ -248,10 +305,10 @@ k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0
 }
 
 // observables of the initial state (output 0)
-template <int N, bool SITES>
+template <int N, bool SITES, bool PAIRS>
 __global__ void __launch_bounds__(64)
 k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, double* __restrict__ out,
-             double* __restrict__ sites) {
+             double* __restrict__ sites, double* __restrict__ pairs) {
   using G = SmallGeo<N>;
   constexpr int R = G::R, DIM = G::DIM;
   __shared__ double2 w[DIM];
@@ -294,25 +351,32 @@ k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, d
     o[7] = 0.0;
   }
   if (SITES) small_site_sums<N>(w, lane, live, sites + (size_t)sel[blockIdx.x] * P.n_t * kSmallSiteStride);
+  if (PAIRS) small_pair_sums<N>(w, lane, live, pairs + (size_t)sel[blockIdx.x] * P.n_t * kSmallPairStride);
 }
 
 }  // namespace
 
 #define DSE_SMALL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
 
+// (SITES, PAIRS) of a launch from the two output pointers
+#define DSE_SMALL_VARIANT(K, q, ...)                                                              \
+  do {                                                                                            \
+    if (sites && pairs)                                                                           \
+      hipLaunchKernelGGL((K<q, true, true>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);   \
+    else if (pairs)                                                                               \
+      hipLaunchKernelGGL((K<q, false, true>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);  \
+    else if (sites)                                                                               \
+      hipLaunchKernelGGL((K<q, true, false>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);  \
+    else                                                                                          \
+      hipLaunchKernelGGL((K<q, false, false>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs); \
+  } while (0)
+
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
-                        const int* iv_set, double* out, hipStream_t st, double* sites) {
+                        const int* iv_set, double* out, hipStream_t st, double* sites, double* pairs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
-  case q:                                                                                                      \
-    if (sites)                                                                                                 \
-      hipLaunchKernelGGL((k_small<q, true>), dim3(count), dim3(64), 0, st, probs, sel, m0, n_int, iv_set, out, \
-                         sites);                                                                               \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_small<q, false>), dim3(count), dim3(64), 0, st, probs, sel, m0, n_int, iv_set,     \
-                         out, sites);                                                                          \
-    break;
+  case q: DSE_SMALL_VARIANT(k_small, q, probs, sel, m0, n_int, iv_set, out); break;
     DSE_SMALL_CASES(X)
 #undef X
     default:
@@ -322,16 +386,11 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 }
 
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites) {
+                             hipStream_t st, double* sites, double* pairs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
-  case q:                                                                                                  \
-    if (sites)                                                                                             \
-      hipLaunchKernelGGL((k_small_obs0<q, true>), dim3(count), dim3(64), 0, st, probs, sel, out, sites);   \
-    else                                                                                                   \
-      hipLaunchKernelGGL((k_small_obs0<q, false>), dim3(count), dim3(64), 0, st, probs, sel, out, sites);  \
-    break;
+  case q: DSE_SMALL_VARIANT(k_small_obs0, q, probs, sel, out); break;
     DSE_SMALL_CASES(X)
 #undef X
     default:

@@ -33,11 +33,12 @@ from .model import (  # noqa: F401  (re-exported API)
     get_derived_frequencies,
     shell_positions_with_rare_center,
 )
-from .problem import OBS_NAMES, Problem, build_problem, site_traces_from_bits, time_grid
+from .problem import OBS_NAMES, Problem, build_problem, pair_traces_from_bits, site_traces_from_bits, time_grid
 
 __all__ = [
     "DipolarRareParams", "get_derived_frequencies", "shell_positions_with_rare_center",
     "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch", "simulate_rare_sites",
+    "simulate_rare_pairs",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
     "simulate_rare_from", "simulate_rare_sequence",
 ]
@@ -75,12 +76,15 @@ SITE_NAMES: Tuple[str, ...] = ("Ix", "Iy", "Iz")
 
 
 def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | None = None,
-                        site_resolved: bool = False) -> List[Tuple]:
+                        site_resolved: bool = False, pair_resolved: bool = False) -> List[Tuple]:
     """Many evolutions at once on one device (same results as calling simulate_rare on each).
 
     ``site_resolved=True``: every result is ``(t, obs, sites)`` with ``sites = {"Ix", "Iy", "Iz"}``,
     each ``(n_sites, steps)`` by reference site index (see simulate_rare_sites); ``t`` and ``obs``
-    are what the default call returns."""
+    are what the default call returns.  ``pair_resolved=True``: every result is
+    ``(t, obs, sites, pairs)`` with ``pairs = {"zz", "zq", "dq"}``, each ``(n_sites, n_sites, steps)``
+    (see simulate_rare_pairs; it needs, and so includes, the site traces)."""
+    site_resolved = site_resolved or pair_resolved
     device = _default_device() if device is None else device
     grids = [time_grid(p) for p in params_list]       # raises ValueError like :620-621
     probs = [build_problem(p, order="engine", reduce=True) for p in params_list]
@@ -100,12 +104,17 @@ def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | 
             if site_resolved:
                 # only for this call: the cached engine is shared with the default path
                 eng.set_option("site_obs", 1)
+            if pair_resolved:
+                eng.set_option("pair_obs", 1)
             try:
                 obs, _ = eng.evolve(t, tol=_tol())
                 traces = [eng.site_traces(slot) for slot in range(len(members))] if site_resolved else None
+                ptraces = [eng.pair_traces(slot) for slot in range(len(members))] if pair_resolved else None
             finally:
                 if site_resolved:
                     eng.set_option("site_obs", 0)
+                if pair_resolved:
+                    eng.set_option("pair_obs", 0)
             for slot, i in enumerate(members):
                 results[i] = (t.copy(), {name: obs[slot, j].copy() for j, name in enumerate(OBS_NAMES)})
                 if site_resolved:
@@ -113,6 +122,10 @@ def simulate_rare_batch(params_list: Sequence[DipolarRareParams], device: int | 
                     by_site = site_traces_from_bits(traces[slot], p.site_of_bit, p.n_sites, p.reduced,
                                                     p.rare_z_const)
                     results[i] += ({name: by_site[c].copy() for c, name in enumerate(SITE_NAMES)},)
+                if pair_resolved:
+                    p = probs[i]
+                    results[i] += (pair_traces_from_bits(ptraces[slot], traces[slot], p.site_of_bit, p.n_sites,
+                                                         p.reduced, p.rare_z_const),)
     eng.clear()
     return results
 
@@ -139,6 +152,19 @@ def simulate_rare_sites(params: DipolarRareParams
     only the sea spins) its row is the constant Iz = -init_x_sign / 2, Ix = Iy = 0, as ``obs["Iz_R"]``.
     No reference counterpart: the reference returns only the seven aggregates."""
     return simulate_rare_batch([params], site_resolved=True)[0]
+
+
+def simulate_rare_pairs(params: DipolarRareParams) -> Tuple[np.ndarray, Dict[str, np.ndarray],
+                                                            Dict[str, np.ndarray], Dict[str, np.ndarray]]:
+    """simulate_rare_sites plus the two-spin correlators: ``(t, obs, sites, pairs)``.
+
+    ``pairs = {"zz", "zq", "dq"}``, each ``(n_sites, n_sites, steps)`` in the reference's site order:
+    zz[k, l] = <Iz_k Iz_l> (real, symmetric), zq[k, l] = <I+_k I-_l> (Hermitian), dq[k, l] =
+    <I+_k I+_l> (symmetric) of the normalised state, so <Ix_k Ix_l> = Re(zq + dq) / 2 and
+    <Iy_k Iy_l> = Re(zq - dq) / 2.  Diagonals: zz = 1/4, zq = 1/2 + <Iz_k>, dq = 0.  When the rare
+    spin is frozen its row and column are zz = Iz_R <Iz_k>, zq = dq = 0.
+    No reference counterpart."""
+    return simulate_rare_batch([params], pair_resolved=True)[0]
 
 
 def problem_to_csr(prob: Problem) -> sp.csr_matrix:

@@ -265,6 +265,34 @@ class Engine:
         self._check(self._L.dse_get_site_obs(self._h, pid, _lib.ptr(out)))
         return out
 
+    def pair_observables(self, pid: int, psi: np.ndarray) -> np.ndarray:
+        """(5, NP): ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of every pair of register bits i < j (at
+        ``problem.pair_index(i, j)``) of the normalised state ``psi`` (dse_pair_observables: the
+        kernel of the option "pair_obs", whatever its value)."""
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        n = self.problems[pid].n_qubits
+        out = np.empty((5, n * (n - 1) // 2))
+        self._check(self._L.dse_pair_observables(self._h, pid, _lib.ptr(x), _lib.ptr(out)))
+        return out
+
+    def pair_traces(self, pid: int) -> np.ndarray:
+        """(5, NP, n_t): the two-spin correlators of register ``pid`` from the last evolve, which
+        must have run with the option "pair_obs" = 1 (RuntimeError otherwise)."""
+        if not 0 <= pid < len(self.problems):
+            raise ValueError("bad problem id")
+        n_t = max(int(self._L.dse_pair_obs_outputs(self._h)), 0)
+        n = self.problems[pid].n_qubits
+        out = np.empty((5, n * (n - 1) // 2, max(n_t, 1)))
+        self._check(self._L.dse_get_pair_obs(self._h, pid, _lib.ptr(out)))
+        return out
+
+    def pair_obs_problems(self) -> int:
+        """Registers whose pair sums the last successful evolve produced."""
+        return int(self._L.dse_pair_obs_problems(self._h))
+
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
         self._check(self._L.dse_get_state(self._h, pid, _lib.ptr(out)))

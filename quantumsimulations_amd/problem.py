@@ -251,3 +251,97 @@ def time_grid(params: DipolarRareParams) -> np.ndarray:
     if params.steps < 2 or params.t_final <= 0.0:
         raise ValueError("Bad time grid: steps >= 2 and t_final > 0.")
     return np.linspace(0.0, params.t_final, params.steps)
+
+
+def pair_index(i: int, j: int) -> int:
+    """Index of the pair of register bits i != j in the engine's pair arrays: j (j - 1) / 2 + i
+    for i < j."""
+    i, j = int(i), int(j)
+    if i == j or i < 0 or j < 0:
+        raise ValueError("a pair is two distinct bits >= 0")
+    if i > j:
+        i, j = j, i
+    return j * (j - 1) // 2 + i
+
+
+def pair_traces_from_bits(pair_bits: np.ndarray, site_bits: np.ndarray, site_of_bit: np.ndarray, n_sites: int,
+                          reduced: bool, rare_z_const: float) -> Dict[str, np.ndarray]:
+    """Two-spin correlators by reference site index from the engine's arrays by register bit.
+
+    ``pair_bits``: ``(5, NP, ...)`` (Engine.pair_traces or Engine.pair_observables: ZZ, Re ZQ, Im ZQ,
+    Re DQ, Im DQ of the pair at ``pair_index(i, j)``); ``site_bits``: ``(3, n, ...)`` of the same
+    states (Engine.site_traces / site_observables).  Returns ``{"zz", "zq", "dq"}``, each
+    ``(n_sites, n_sites, ...)``: zz[k, l] = <Iz_k Iz_l> (real, symmetric), zq[k, l] = <I+_k I-_l>
+    (complex, Hermitian), dq[k, l] = <I+_k I+_l> (complex, symmetric).  The diagonals are the
+    spin-1/2 identities zz = 1/4, zq = 1/2 + <Iz_k>, dq = 0.  In a reduced register the frozen rare
+    spin (the last site) is not a bit: its row and column are zz = ``rare_z_const`` <Iz_k>,
+    zq = dq = 0 (why the site traces are needed)."""
+    pb = np.asarray(pair_bits, dtype=np.float64)
+    sb = np.asarray(site_bits, dtype=np.float64)
+    sob = np.asarray(site_of_bit, dtype=np.int64)
+    n = sob.size
+    if pb.ndim < 2 or pb.shape[0] != 5 or pb.shape[1] != n * (n - 1) // 2:
+        raise ValueError("pair_bits must have shape (5, n (n - 1) / 2, ...) with n = len(site_of_bit)")
+    if sb.ndim < 2 or sb.shape[0] != 3 or sb.shape[1] != n or sb.shape[2:] != pb.shape[2:]:
+        raise ValueError("site_bits must have shape (3, n, ...) with the trailing shape of pair_bits")
+    expect = n_sites - 1 if reduced else n_sites
+    if n != expect or sorted(sob.tolist()) != list(range(n)):
+        raise ValueError("site_of_bit must be a permutation of the register's sites")
+    tail = pb.shape[2:]
+    zz = np.zeros((n_sites, n_sites) + tail)
+    zq = np.zeros((n_sites, n_sites) + tail, dtype=np.complex128)
+    dq = np.zeros((n_sites, n_sites) + tail, dtype=np.complex128)
+    for j in range(n):
+        for i in range(j):
+            p = pair_index(i, j)
+            k, l = int(sob[i]), int(sob[j])
+            zz[k, l] = zz[l, k] = pb[0, p]
+            zq[k, l] = pb[1, p] + 1j * pb[2, p]
+            zq[l, k] = pb[1, p] - 1j * pb[2, p]
+            dq[k, l] = dq[l, k] = pb[3, p] + 1j * pb[4, p]
+    for b in range(n):
+        k = int(sob[b])
+        zz[k, k] = 0.25
+        zq[k, k] = 0.5 + sb[2, b]
+    if reduced:
+        r = n_sites - 1
+        for b in range(n):
+            k = int(sob[b])
+            zz[k, r] = zz[r, k] = rare_z_const * sb[2, b]
+        zz[r, r] = 0.25
+        zq[r, r] = 0.5 + rare_z_const
+    return {"zz": zz, "zq": zq, "dq": dq}
+
+
+def energy_partition(prob: Problem, site_bits: np.ndarray, pair_bits: np.ndarray) -> Dict[str, np.ndarray]:
+    """<H> of the normalised state(s), term by term, from the site sums ``(3, n, ...)`` and the pair
+    sums ``(5, NP, ...)`` in register-bit order and the Problem's own tables:
+
+        <H> = shift + sum_b field[b] Z_b + 2 sum_b (re0_b X_b - im0_b Y_b)
+              + sum_{i<j} zz[i, j] ZZ_ij + 2 sum_{i<j} pair[i, j] Re DQ_ij
+
+    Returns ``{"shift", "field", "drive", "zz", "pair", "total"}`` (each of the trailing shape)."""
+    sb = np.asarray(site_bits, dtype=np.float64)
+    pb = np.asarray(pair_bits, dtype=np.float64)
+    n = prob.n_qubits
+    if sb.ndim < 2 or sb.shape[:2] != (3, n):
+        raise ValueError("site_bits must have shape (3, n, ...)")
+    if pb.ndim < 2 or pb.shape[:2] != (5, n * (n - 1) // 2) or pb.shape[2:] != sb.shape[2:]:
+        raise ValueError("pair_bits must have shape (5, n (n - 1) / 2, ...) with the trailing shape of site_bits")
+    tail = sb.shape[2:]
+    flip = np.asarray(prob.flip, dtype=np.float64).reshape(n, 4)
+    e_field = np.zeros(tail)
+    e_drive = np.zeros(tail)
+    e_zz = np.zeros(tail)
+    e_pair = np.zeros(tail)
+    for b in range(n):
+        e_field = e_field + prob.field[b] * sb[2, b]
+        e_drive = e_drive + 2.0 * (flip[b, 0] * sb[0, b] - flip[b, 1] * sb[1, b])
+    for j in range(n):
+        for i in range(j):
+            p = pair_index(i, j)
+            e_zz = e_zz + prob.zz[i, j] * pb[0, p]
+            e_pair = e_pair + 2.0 * prob.pair[i, j] * pb[3, p]
+    e_shift = np.full(tail, float(prob.shift))
+    return {"shift": e_shift, "field": e_field, "drive": e_drive, "zz": e_zz, "pair": e_pair,
+            "total": e_shift + e_field + e_drive + e_zz + e_pair}
