@@ -50,6 +50,20 @@ extern "C" int dse_bessel_j(double z, int kmax, double* out, double tol, int* de
     if (degree) *degree = 1;
     return DSE_OK;
   }
+  if (z < 1e-40) {
+    // The recurrence below multiplies values of up to 1e250 by 2k/z and overflows (inf - inf: NaN
+    // in every coefficient) for z below ~1e-58 k.  A register whose spectral half-width is zero
+    // (H a multiple of 1: alpha clamped to 1e-300) has such a z.  Here the ascending series'
+    // first term J_k = (z/2)^k / k! is exact in fp64 (the next is smaller by z^2 / 4(k + 1)).
+    out[0] = 1.0;
+    for (int k = 1; k <= kmax; ++k) out[k] = out[k - 1] * (0.5 * z / k);  // underflows to 0
+    if (degree) {
+      int d = 1;
+      while (d < kmax && out[d + 1] > tol) ++d;  // decreasing in k
+      *degree = d;
+    }
+    return DSE_OK;
+  }
   // start index: beyond both kmax and the turning point z, plus a margin for decay below 1e-300
   const int m0 = (int)std::ceil(std::fmax((double)kmax, z) + 60.0 + 12.0 * std::cbrt(z + 1.0));
   const int m = m0 + (m0 & 1);  // even

@@ -205,6 +205,27 @@ def test_native_bessel_accuracy(z):
         assert np.all(np.abs(j[deg + 1:]) <= 1e-14) and abs(j[deg]) > 1e-14
 
 
+@pytest.mark.parametrize("z", [5e-324, 5e-303, 1e-100, 1e-60, 1e-57, 0.99e-40, 1e-40, 1e-20, 1e-8])
+def test_native_bessel_tiny_arguments(z):
+    """A register whose H is a multiple of 1 has spectral half-width 0 (clamped to 1e-300), so z =
+    alpha dt ~ 1e-302: Miller's recurrence overflowed to NaN below z ~ 1e-58.  For z <= 1e-8 the
+    ascending series' first term (z/2)^k / k! is J_k(z) to a relative z^2 / 4(k + 1) < 2.5e-17.
+    Below 1e-40 the library takes that term by a product of k factors (2 roundings each; the
+    reference here: a power and a division, 3 more): (2k + 3) eps / 2, plus the smallest subnormal.
+    Above, the recurrence: test_native_bessel_accuracy's absolute 5e-14."""
+    from math import factorial
+    from quantumsimulations_amd.engine import bessel_native
+    kmax = 72
+    j, deg = bessel_native(z, kmax, 1e-14)
+    assert np.all(np.isfinite(j)) and deg == 1
+    assert j[0] == 1.0
+    for k in (1, 2, 3, 7):
+        ref = (z / 2.0) ** k / factorial(k)
+        bound = (k + 2) * np.finfo(float).eps * ref + 5e-324 if z < 1e-40 else 5e-14
+        assert abs(j[k] - ref) <= bound, (k, j[k], ref)
+    assert np.all(j >= 0.0) and np.all(j[8:] < 1e-60)
+
+
 def test_create_without_device_fails_cleanly():
     lib = _lib_or_skip()
     if lib.dse_device_count() > 0:
