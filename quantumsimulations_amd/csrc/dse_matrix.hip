@@ -13,7 +13,7 @@
 //             (c_k = (2 - delta_k0) J_k(alpha dt)); U_rc = i^{|c| - |r|} U'_rc is written in the
 //             computational frame.  Half the FP64 work and half the LDS bytes of the complex
 //             column build, no input columns in HBM, and the two sums stay in registers.
-//   k_symv    y = U x over the 128 x 128 tiles on and above the diagonal (U_cr = s_r s_c U_rc),
+//   k_symv    y = U x over the 64 x 64 tiles (kSymvBlock) on and above the diagonal (U_cr = s_r s_c U_rc),
 //   k_symv_reduce   the per-tile partial sums in fixed order (deterministic, no atomics).
 #include <type_traits>
 

@@ -12,6 +12,11 @@ column mode + rocBLAS zgemv.
 * drive phases off pi/2 (complex drive coefficients): the complex build + zgemv, same traces as the
   per-interval engine
 * a non-uniform grid or a second register keeps the per-interval kernels
+
+These cases are the physical geometry at n = 10 and 12, whose list of thread-bit pairs is full.  Every
+tile size (n = 10 .. 13), the real-drive form, sparse pair lists, the position of the basis column,
+option symv_fused and buffer reuse across sizes are in test_gpu_matrix_cases.py, against a CPU
+propagation of raw-table problems.
 """
 import numpy as np
 import pytest
