@@ -6,9 +6,12 @@
 // the rotating frame, :469-471, :514-530), so the engine propagates each output interval
 // exactly:  exp(-i H dt) = exp(-i beta dt) sum_k (2 - delta_k0) (-i)^k J_k(alpha dt) T_k(Ht),
 // Ht = (H - beta)/alpha with spectrum(H) inside [beta - alpha, beta + alpha].
+#include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../../include/dse.h"
@@ -87,3 +90,50 @@ extern "C" int dse_bessel_j(double z, int kmax, double* out, double tol, int* de
   }
   return DSE_OK;
 }
+
+// cheb_rows (declared in dse_internal.h, not exported): a_k = e^{-i beta tau} (2 - delta_k0) (-i)^k
+// J_k(alpha tau) of every offset tau of every set
+namespace dse {
+__attribute__((visibility("hidden")))
+int cheb_rows(double alpha, double beta, const std::vector<std::vector<double>>& set_tau, int M, double tol,
+              double max_degree, int* deg_out, std::vector<std::pair<double, double>>* rows, int* kmax_over) {
+  const int n_sets = (int)set_tau.size();
+  int deg = 1;
+  std::vector<std::vector<double>> J((size_t)n_sets * M);
+  std::vector<int> deg_sj((size_t)n_sets * M, 0);
+  for (int s = 0; s < n_sets; ++s)
+    for (size_t j = 0; j < set_tau[s].size(); ++j) {
+      const double z = alpha * set_tau[s][j];
+      const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
+      if (kmax > max_degree) {
+        *kmax_over = kmax;
+        return DSE_ERR_CONVERGENCE;
+      }
+      std::vector<double>& Jv = J[(size_t)s * M + j];
+      Jv.resize(kmax + 1);
+      int d = 1;
+      if (dse_bessel_j(z, kmax, Jv.data(), tol, &d) != DSE_OK) return DSE_ERR_ARG;
+      deg_sj[(size_t)s * M + j] = d;
+      deg = std::max(deg, d);
+    }
+  *deg_out = deg;
+  const int kcap1 = deg + 1;
+  rows->assign((size_t)n_sets * M * (kcap1 + 1), std::make_pair(0.0, 0.0));
+  for (int s = 0; s < n_sets; ++s)
+    for (size_t j = 0; j < set_tau[s].size(); ++j) {
+      const std::vector<double>& Jv = J[(size_t)s * M + j];
+      const int dj = deg_sj[(size_t)s * M + j];
+      const double ph = -beta * set_tau[s][j];
+      const std::complex<double> e(std::cos(ph), std::sin(ph));
+      std::complex<double> mi(1.0, 0.0);  // (-i)^k
+      std::pair<double, double>* row = rows->data() + ((size_t)s * M + j) * (kcap1 + 1);
+      row[0] = std::make_pair((double)dj, 0.0);
+      for (int k = 0; k <= dj; ++k) {
+        const std::complex<double> a = e * mi * ((k == 0 ? 1.0 : 2.0) * Jv[k]);
+        row[1 + k] = std::make_pair(a.real(), a.imag());
+        mi *= std::complex<double>(0.0, -1.0);
+      }
+    }
+  return DSE_OK;
+}
+}  // namespace dse

@@ -4,8 +4,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 namespace dse {
+
+// Chebyshev rows of one register (dse_host.cpp, host only): the series of exp(-i (alpha x + beta) tau)
+// on x in [-1, 1] for every offset set_tau[set][j], truncated where dse_bessel_j drops below tol.
+// rows: [set][j < M] x (deg + 2) pairs (re, im), [0].re the row's degree, [1 + k] the coefficient
+// a_k, zero past the degree and for j >= set_tau[set].size(); *deg the largest row degree (>= 1).
+// DSE_ERR_CONVERGENCE when an offset needs more than max_degree terms (*kmax_over: how many),
+// DSE_ERR_ARG when dse_bessel_j fails.  Internal to the library (hidden: not an exported symbol).
+__attribute__((visibility("hidden"))) int cheb_rows(double alpha, double beta, const std::vector<std::vector<double>>& set_tau, int M, double tol,
+              double max_degree, int* deg, std::vector<std::pair<double, double>>* rows, int* kmax_over);
 
 enum { MODE_APPLY = 0, MODE_FIRST = 1, MODE_GEN = 2 };
 

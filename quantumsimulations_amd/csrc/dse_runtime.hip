@@ -30,6 +30,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <tuple>
 #include <deque>
 #include <vector>
 
@@ -106,10 +107,43 @@ struct HostProblem {
   double* d_init_amp = nullptr;
 };
 
+int fail(dse_ctx* c, int code, const std::string& msg);
+
+// One grow-only device buffer of cap elements.  reserve() keeps a buffer that is large enough and
+// otherwise frees it before it allocates the larger one (the contents are not kept); after a failed
+// allocation the buffer is empty, cap = 0.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;  // in elements
+  void release() {
+    if (p) (void)hipFree(p), p = nullptr;
+    cap = 0;
+  }
+  // what: the message of DSE_ERR_OOM; with_bytes appends " (<size> bytes)"
+  int reserve(dse_ctx* ctx, size_t n, const char* what, bool with_bytes = false) {
+    if (n <= cap) return DSE_OK;
+    release();
+    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      return fail(ctx, DSE_ERR_OOM, with_bytes ? std::string(what) + " (" + std::to_string(n * sizeof(T)) + " bytes)" : what);
+    }
+    cap = n;
+    return DSE_OK;
+  }
+};
+template <class... B>
+void release_all(B&... b) { (b.release(), ...); }
+
+// What a lane group launches.  Tiles: k_interval (persistent) or the step / Walsh-Hadamard kernels (streaming)
+// over problems of `tiles` tiles each; Mixed: 1- and 2-tile problems in one k_interval launch; Span: k_span; Real: k_real
+enum class GroupKind { Tiles, Mixed, Span, Real };
+
 // One stream's share of the problems, grouped by tile size.
 struct LaneGroup {
   int L = 0;
-  int tiles = 1;            // tiles per problem (persistent mode: 1 or 2)
+  GroupKind kind = GroupKind::Tiles;
+  int tiles = 1;            // tiles per problem of kind Tiles (persistent mode: 1 or 2); else 0
   int wht_groups = 0;       // > 0: every problem of the group runs on the Walsh-Hadamard engine
   std::vector<std::pair<int, int>> wht_regs;  // partitioned registers: (first shard, degree)
   int64_t off = 0;          // first position in the global item array
@@ -117,7 +151,7 @@ struct LaneGroup {
   std::vector<int> active;     // active[k] = items with degree >= k (prefix of the group)
   std::vector<double> bytes;   // bytes[k] = algorithmic HBM bytes of the term-k launch
   std::vector<double> flops;   // flops[k] = algorithmic flops of the term-k launch
-  // spanning registers (tiles < 0): k_span<span_L, span_rb> over span_count launch items from
+  // spanning registers (kind Span): k_span<span_L, span_rb> over span_count launch items from
   // span_off in dse_ctx::d_span_items (tiles of one register 8 apart, padding items x = -1)
   int span_L = 0, span_rb = 0;
   int64_t span_off = 0, span_count = 0;
@@ -128,7 +162,6 @@ struct LaneGroup {
   std::vector<double> span_am, span_fl;  // per launch: amplitudes x terms, algorithmic flops
   // real-component registers: k_real over real_count items (problem, component) from real_off in
   // dse_ctx::d_real_items, then k_real_combine over real_np items (problem, 0) from real_poff
-  bool real = false;
   int64_t real_off = 0, real_count = 0, real_poff = 0, real_np = 0;
 };
 struct Lane {
@@ -161,31 +194,29 @@ struct dse_ctx {
   int2* d_items_iv = nullptr;       // the same, 2-tile groups reordered for the interval kernel
   std::vector<int64_t> item_pos;    // first item position of every problem (evolve layout)
   int64_t total_items = 0;
-  double* d_partial = nullptr;
+  DevBuf<double> d_partial;
   size_t partial_slots = 0;
   // site-resolved observables (option "site_obs", dse_site_observables): a second partial arena for
   // k_obs_sites, site_S doubles per tile and slot (site_stride of the context's widest register),
   // and the results of the last evolve, per register [3][n][n_t] (loopback group: shard 0's entry)
   int site_obs = 0;
-  double* d_site_partial = nullptr;
+  DevBuf<double> d_site_partial;
   size_t site_slots = 0;
   int site_S = 0;
   std::vector<std::vector<double>> site_store;
   int site_nt = 0;                  // output times of site_store (0: none)
-  double* d_small_sites = nullptr;  // small engine: [problem][n_t][kSmallSiteStride] raw site sums
-  size_t small_sites_cap = 0;
+  DevBuf<double> d_small_sites;      // small engine: [problem][n_t][kSmallSiteStride] raw site sums
   // two-spin correlators (option "pair_obs", dse_pair_observables): a third partial arena for
   // k_obs_pairs, pair_S doubles per tile and slot (pair_stride of the context's widest register),
   // and the results of the last evolve, per register [5][NP][n_t] (loopback group: shard 0's entry)
   int pair_obs = 0;
-  double* d_pair_partial = nullptr;
+  DevBuf<double> d_pair_partial;
   size_t pair_slots = 0;
   int pair_S = 0;
   std::vector<std::vector<double>> pair_store;
   int pair_nt = 0;                  // output times of pair_store (0: none)
   int pair_problems = 0;            // registers with pair sums in the last successful evolve
-  double* d_small_pairs = nullptr;  // small engine: [problem][n_t][kSmallPairStride] raw pair sums
-  size_t small_pairs_cap = 0;
+  DevBuf<double> d_small_pairs;      // small engine: [problem][n_t][kSmallPairStride] raw pair sums
   std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
   bool prepared = false;
   bool evolved = false;
@@ -215,21 +246,14 @@ struct dse_ctx {
   int handoff_fallbacks = 0;        // this evolve call re-ran on the streaming kernels after a hand-off timeout (0/1)
   bool rerun = false;               // that re-run: the dense engine's results of the first pass are kept
   int* d_err_cur = nullptr;         // the hand-off error word of the running persistent evolve (else null)
-  double* d_allreduce = nullptr;    // RCCL all-reduce staging buffer of the observable sums (grow-only)
-  size_t allreduce_cap = 0;         // in doubles
-  int* d_flags = nullptr;           // hand-off flags (2 tiles x kIvWaves per problem) + error word
-  size_t flags_cap = 0;
-  double2* d_xslots = nullptr;      // hand-off slots of the interval kernel
-  size_t xslot_cap = 0;             // in amplitudes
-  double2* d_xacc = nullptr;        // intermediate outputs of multi-output launches
-  size_t xacc_cap = 0;              // in amplitudes
+  DevBuf<double> d_allreduce;       // RCCL all-reduce staging buffer of the observable sums
+  DevBuf<int> d_flags;              // hand-off flags (2 tiles x kIvWaves per problem) + error word
+  DevBuf<double2> d_xslots;         // hand-off slots of the interval kernel
+  DevBuf<double2> d_xacc;           // intermediate outputs of multi-output launches
   // per-evolve uploads, one device arena each (one copy per evolve, not one per problem)
-  unsigned char* d_coef = nullptr;  // Chebyshev coefficient rows of every problem
-  size_t coef_cap = 0;
-  unsigned char* d_sm_coef = nullptr;  // small-engine coefficients and degrees
-  size_t sm_coef_cap = 0;
-  BasisInit* d_init = nullptr;      // psi(t0) list
-  size_t init_cap = 0;
+  DevBuf<unsigned char> d_coef;     // Chebyshev coefficient rows of every problem
+  DevBuf<unsigned char> d_sm_coef;  // small-engine coefficients and degrees
+  DevBuf<BasisInit> d_init;         // psi(t0) list
   int outputs_per_launch = 2;       // M of the interval kernel (dse_evolve picks 1 on coarse grids)
   int span_outputs = 4;             // M when every register spans (k_span, staggered sums)
   int64_t probe_items = 0;          // 0: all items
@@ -258,12 +282,9 @@ struct dse_ctx {
   int swap_overlap = 1;
   hipStream_t swap_stream = nullptr;
   hipEvent_t swap_ev[8] = {};
-  SmallProb* d_small = nullptr;
-  size_t small_cap = 0;             // descriptors allocated
-  double* d_small_out = nullptr;    // [problem][n_t][8] raw observable sums
-  size_t small_out_cap = 0;
-  int* d_small_aux = nullptr;       // problem selections per register size, interval -> set map
-  size_t small_aux_cap = 0;
+  DevBuf<SmallProb> d_small;        // descriptors
+  DevBuf<double> d_small_out;       // [problem][n_t][8] raw observable sums
+  DevBuf<int> d_small_aux;          // problem selections per register size, interval -> set map
   // dense eigen-propagator engine (dse_dense.h): option "dense" 0 off, 1 when cheaper than the
   // Chebyshev propagator by the cost model of dense_cheaper (default), 2 for every eligible register
   int dense = 1;
@@ -273,8 +294,7 @@ struct dse_ctx {
   // matrix mode's device buffers (U, the states, the products' partial sums, tables), kept across
   // evolves of the same register size (simulate_rare calls one register at a time; a 2^12 register
   // holds 256 MiB of U) and released by dse_destroy or when a larger register needs more
-  unsigned char* d_mx = nullptr;
-  size_t mx_cap = 0;
+  DevBuf<unsigned char> d_mx;
   // option "symv_fused": each product's reduction inside the product's launch (agent-scope counters
   // with a release per workgroup): measured 22.9 vs 10.4 ms for config 2, so off by default
   int symv_fused = 0;
@@ -289,23 +309,15 @@ struct dse_ctx {
   // real-component mode (dse_real.hip, option "real", default 0): registers of 13 or 14 qubits with
   // imaginary drives run as two real recurrences, one workgroup per component, no hand-off
   int real_mode = 0;
-  unsigned char* d_real = nullptr;  // [a | b] inputs and propagator sums of the real-mode registers
-  size_t real_cap = 0;
-  unsigned char* d_real_tab = nullptr;
-  size_t real_tab_cap = 0;
-  int2* d_real_items = nullptr;
-  size_t real_items_cap = 0;
+  DevBuf<double2> d_real;           // [a | b] inputs and propagator sums of the real-mode registers
+  DevBuf<unsigned char> d_real_tab;
+  DevBuf<int2> d_real_items;
   int span_rb = 0;
-  SpanDesc* d_span = nullptr;       // per problem
-  size_t span_cap = 0;
-  unsigned char* d_span_tab = nullptr;
-  size_t span_tab_cap = 0;
-  double2* d_span_slots = nullptr;  // hand-off slots of the spanned registers
-  size_t span_slot_cap = 0;         // in amplitudes
-  int* d_span_flags = nullptr;
-  size_t span_flag_cap = 0;
-  int2* d_span_items = nullptr;
-  size_t span_items_cap = 0;
+  DevBuf<SpanDesc> d_span;          // per problem
+  DevBuf<unsigned char> d_span_tab;
+  DevBuf<double2> d_span_slots;     // hand-off slots of the spanned registers
+  DevBuf<int> d_span_flags;
+  DevBuf<int2> d_span_items;
 
   hipStream_t dense_stream = nullptr;
   rocblas_handle blas = nullptr;
@@ -452,18 +464,12 @@ struct Arena {
   }
 };
 
-// The arena's device copy: grows *dev to fit, then one copy on stream st (stream-ordered before
+// The arena's device copy: grows dev to fit, then one copy on stream st (stream-ordered before
 // every later launch on st; the caller synchronises st before other streams use it).
-int upload_arena(dse_ctx* ctx, const Arena& a, unsigned char** dev, size_t* cap, hipStream_t st) {
+int upload_arena(dse_ctx* ctx, const Arena& a, DevBuf<unsigned char>& dev, hipStream_t st) {
   if (a.host.empty()) return DSE_OK;
-  if (a.host.size() > *cap) {
-    if (*dev) (void)hipFree(*dev), *dev = nullptr;
-    *cap = 0;
-    if (hipMalloc(dev, a.host.size()) != hipSuccess)
-      return fail(ctx, DSE_ERR_OOM, "coefficient allocation failed (" + std::to_string(a.host.size()) + " bytes)");
-    *cap = a.host.size();
-  }
-  HIPC(hipMemcpyAsync(*dev, a.host.data(), a.host.size(), hipMemcpyHostToDevice, st));
+  if (int rc = dev.reserve(ctx, a.host.size(), "coefficient allocation failed", true)) return rc;
+  HIPC(hipMemcpyAsync(dev.p, a.host.data(), a.host.size(), hipMemcpyHostToDevice, st));
   HIPC(hipStreamSynchronize(st));  // the host bytes may be released after return
   return DSE_OK;
 }
@@ -501,47 +507,15 @@ void free_device(dse_ctx* ctx) {
   if (ctx->d_probs) (void)hipFree(ctx->d_probs), ctx->d_probs = nullptr;
   if (ctx->d_items) (void)hipFree(ctx->d_items), ctx->d_items = nullptr;
   if (ctx->d_items_iv) (void)hipFree(ctx->d_items_iv), ctx->d_items_iv = nullptr;
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial), ctx->d_partial = nullptr;
-  if (ctx->d_site_partial) (void)hipFree(ctx->d_site_partial), ctx->d_site_partial = nullptr;
-  ctx->site_slots = 0;
-  if (ctx->d_small_sites) (void)hipFree(ctx->d_small_sites), ctx->d_small_sites = nullptr;
-  ctx->small_sites_cap = 0;
+  release_all(ctx->d_partial, ctx->d_site_partial, ctx->d_pair_partial, ctx->d_small_sites, ctx->d_small_pairs,
+              ctx->d_flags, ctx->d_xslots, ctx->d_xacc, ctx->d_real, ctx->d_real_tab, ctx->d_real_items, ctx->d_span,
+              ctx->d_span_tab, ctx->d_span_slots, ctx->d_span_flags, ctx->d_span_items, ctx->d_coef, ctx->d_sm_coef,
+              ctx->d_init, ctx->d_small, ctx->d_small_out, ctx->d_small_aux, ctx->d_allreduce);
+  ctx->site_slots = ctx->pair_slots = 0;
   ctx->site_store.clear();
-  ctx->site_nt = 0;
-  if (ctx->d_pair_partial) (void)hipFree(ctx->d_pair_partial), ctx->d_pair_partial = nullptr;
-  ctx->pair_slots = 0;
-  if (ctx->d_small_pairs) (void)hipFree(ctx->d_small_pairs), ctx->d_small_pairs = nullptr;
-  ctx->small_pairs_cap = 0;
   ctx->pair_store.clear();
-  ctx->pair_nt = 0;
-  ctx->pair_problems = 0;
+  ctx->site_nt = ctx->pair_nt = ctx->pair_problems = 0;
   for (auto& kv : ctx->zzlo_tables) (void)hipFree(kv.second);
-  if (ctx->d_flags) (void)hipFree(ctx->d_flags), ctx->d_flags = nullptr;
-  ctx->flags_cap = 0;
-  if (ctx->d_xslots) (void)hipFree(ctx->d_xslots), ctx->d_xslots = nullptr;
-  ctx->xslot_cap = 0;
-  if (ctx->d_xacc) (void)hipFree(ctx->d_xacc), ctx->d_xacc = nullptr;
-  ctx->xacc_cap = 0;
-  if (ctx->d_span) (void)hipFree(ctx->d_span), ctx->d_span = nullptr;
-  if (ctx->d_real) (void)hipFree(ctx->d_real), ctx->d_real = nullptr;
-  if (ctx->d_real_tab) (void)hipFree(ctx->d_real_tab), ctx->d_real_tab = nullptr;
-  if (ctx->d_real_items) (void)hipFree(ctx->d_real_items), ctx->d_real_items = nullptr;
-  ctx->real_cap = ctx->real_tab_cap = ctx->real_items_cap = 0;
-  if (ctx->d_span_tab) (void)hipFree(ctx->d_span_tab), ctx->d_span_tab = nullptr;
-  if (ctx->d_span_slots) (void)hipFree(ctx->d_span_slots), ctx->d_span_slots = nullptr;
-  if (ctx->d_span_flags) (void)hipFree(ctx->d_span_flags), ctx->d_span_flags = nullptr;
-  if (ctx->d_span_items) (void)hipFree(ctx->d_span_items), ctx->d_span_items = nullptr;
-  ctx->span_cap = ctx->span_tab_cap = ctx->span_slot_cap = ctx->span_flag_cap = ctx->span_items_cap = 0;
-  if (ctx->d_coef) (void)hipFree(ctx->d_coef), ctx->d_coef = nullptr;
-  if (ctx->d_sm_coef) (void)hipFree(ctx->d_sm_coef), ctx->d_sm_coef = nullptr;
-  if (ctx->d_init) (void)hipFree(ctx->d_init), ctx->d_init = nullptr;
-  ctx->coef_cap = ctx->sm_coef_cap = ctx->init_cap = 0;
-  if (ctx->d_small) (void)hipFree(ctx->d_small), ctx->d_small = nullptr;
-  if (ctx->d_small_out) (void)hipFree(ctx->d_small_out), ctx->d_small_out = nullptr;
-  if (ctx->d_small_aux) (void)hipFree(ctx->d_small_aux), ctx->d_small_aux = nullptr;
-  ctx->small_cap = ctx->small_out_cap = ctx->small_aux_cap = 0;
-  if (ctx->d_allreduce) (void)hipFree(ctx->d_allreduce), ctx->d_allreduce = nullptr;
-  ctx->allreduce_cap = 0;
   ctx->zzlo_tables.clear();
   ctx->partial_slots = 0;
   ctx->total_items = 0;
@@ -1106,14 +1080,9 @@ int xchg_allreduce_host(dse_ctx* ctx, double* v, size_t count, hipStream_t st) {
       return fail(ctx, DSE_ERR_HIP, "exchange callback (all-reduce) failed");
     return DSE_OK;
   }
-  if (ctx->allreduce_cap < count) {  // one staging buffer per context, grown on demand
-    if (ctx->d_allreduce) (void)hipFree(ctx->d_allreduce), ctx->d_allreduce = nullptr;
-    ctx->allreduce_cap = 0;
-    if (hipMalloc(&ctx->d_allreduce, count * sizeof(double)) != hipSuccess)
-      return fail(ctx, DSE_ERR_OOM, "all-reduce staging allocation failed");
-    ctx->allreduce_cap = count;
-  }
-  double* d = ctx->d_allreduce;
+  // one staging buffer per context, grown on demand
+  if (int rc = ctx->d_allreduce.reserve(ctx, count, "all-reduce staging allocation failed")) return rc;
+  double* d = ctx->d_allreduce.p;
   hipError_t e = hipMemcpyAsync(d, v, count * sizeof(double), hipMemcpyHostToDevice, st);
   const ncclResult_t r = ncclAllReduce(d, d, count, ncclFloat64, ncclSum, ctx->comm, st);
   if (e == hipSuccess) e = hipMemcpyAsync(v, d, count * sizeof(double), hipMemcpyDeviceToHost, st);
@@ -1213,11 +1182,28 @@ int wht_run(dse_ctx* ctx, int wl, int G, const std::vector<std::pair<const int2*
   return DSE_OK;
 }
 
+// The three partial arenas (aggregate, site and pair observables) hold the sums of up to `slots`
+// output times before a flush copies them back; one slot of any of them stays within this cap
+constexpr int64_t kPartialCapBytes = 256ll << 20;
+
+int widest_register(const dse_ctx* ctx) {  // qubits (1 for an empty context)
+  int n_max = 1;
+  for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
+  return n_max;
+}
+
+// slots per flush of an arena of per_slot bytes per output time: what the cap holds, at most the
+// n_t outputs there are and at least the M outputs of one launch (they share a flush)
+size_t partial_chunk(int64_t per_slot, int M, int n_t) {
+  return (size_t)std::max<int64_t>(M, std::min<int64_t>(n_t, std::max<int64_t>(1, kPartialCapBytes / per_slot)));
+}
+
 int ensure_partial(dse_ctx* ctx, size_t slots) {
   if (ctx->partial_slots >= slots) return DSE_OK;
-  if (ctx->d_partial) (void)hipFree(ctx->d_partial), ctx->d_partial = nullptr;
-  if (hipMalloc(&ctx->d_partial, slots * ctx->total_items * 8 * sizeof(double)) != hipSuccess)
-    return fail(ctx, DSE_ERR_OOM, "device allocation of observable partials failed");
+  ctx->partial_slots = 0;
+  ctx->d_partial.release();
+  if (int rc = ctx->d_partial.reserve(ctx, slots * ctx->total_items * 8, "device allocation of observable partials failed"))
+    return rc;
   ctx->partial_slots = slots;
   return DSE_OK;
 }
@@ -1225,14 +1211,13 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
 // the second arena, for k_obs_sites: slots x total_items x S doubles, S = site_stride of the widest
 // register of the context
 int ensure_site_partial(dse_ctx* ctx, size_t slots) {
-  int n_max = 1;
-  for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
-  const int S = site_stride(n_max);
+  const int S = site_stride(widest_register(ctx));
   if (ctx->site_slots >= slots && ctx->site_S == S) return DSE_OK;
-  if (ctx->d_site_partial) (void)hipFree(ctx->d_site_partial), ctx->d_site_partial = nullptr;
   ctx->site_slots = 0;
-  if (hipMalloc(&ctx->d_site_partial, slots * ctx->total_items * S * sizeof(double)) != hipSuccess)
-    return fail(ctx, DSE_ERR_OOM, "device allocation of site-observable partials failed");
+  ctx->d_site_partial.release();
+  if (int rc = ctx->d_site_partial.reserve(ctx, slots * ctx->total_items * S,
+                                           "device allocation of site-observable partials failed"))
+    return rc;
   ctx->site_slots = slots;
   ctx->site_S = S;
   return DSE_OK;
@@ -1264,14 +1249,6 @@ void reset_site_store(dse_ctx* ctx, int n_t) {
 
 // ---- two-spin correlators (option pair_obs): the third arena and its host store ---------------
 
-constexpr int64_t kPartialCapBytes = 256ll << 20;  // one output slot of a partial arena
-
-int pair_n_max(const dse_ctx* ctx) {
-  int n_max = 1;
-  for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
-  return n_max;
-}
-
 // Refusals of the option and of the hook, decided before any work (after prepare: the tile count is
 // known): no register partitioned over processes, and one output slot of the arena, tiles x
 // pair_stride(n_max) doubles, within the cap of the other arenas
@@ -1280,22 +1257,23 @@ int pair_refusal(dse_ctx* ctx, const char* who) {
     if (P.dist)
       return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over "
                                         "processes (the all-reduce of the pair sums is not implemented)");
-  const int64_t per_slot = ctx->total_items * (int64_t)pair_stride(pair_n_max(ctx)) * 8;
+  const int64_t per_slot = ctx->total_items * (int64_t)pair_stride(widest_register(ctx)) * 8;
   if (per_slot > kPartialCapBytes)
     return fail(ctx, DSE_ERR_ARG, std::string(who) + ": the pair sums of one output (" + std::to_string(ctx->total_items) +
-                                      " tiles x " + std::to_string(pair_stride(pair_n_max(ctx))) +
+                                      " tiles x " + std::to_string(pair_stride(widest_register(ctx))) +
                                       " doubles) exceed the 256 MiB partial arena");
   return DSE_OK;
 }
 
 // slots x total_items x S doubles, S = pair_stride of the widest register of the context
 int ensure_pair_partial(dse_ctx* ctx, size_t slots) {
-  const int S = pair_stride(pair_n_max(ctx));
+  const int S = pair_stride(widest_register(ctx));
   if (ctx->pair_slots >= slots && ctx->pair_S == S) return DSE_OK;
-  if (ctx->d_pair_partial) (void)hipFree(ctx->d_pair_partial), ctx->d_pair_partial = nullptr;
   ctx->pair_slots = 0;
-  if (hipMalloc(&ctx->d_pair_partial, slots * std::max<int64_t>(1, ctx->total_items) * S * sizeof(double)) != hipSuccess)
-    return fail(ctx, DSE_ERR_OOM, "device allocation of pair-observable partials failed");
+  ctx->d_pair_partial.release();
+  if (int rc = ctx->d_pair_partial.reserve(ctx, slots * std::max<int64_t>(1, ctx->total_items) * S,
+                                           "device allocation of pair-observable partials failed"))
+    return rc;
   ctx->pair_slots = slots;
   ctx->pair_S = S;
   return DSE_OK;
@@ -1334,7 +1312,7 @@ void reset_pair_store(dse_ctx* ctx, int n_t) {
 int flush_pair_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t) {
   const size_t S = (size_t)ctx->pair_S;
   std::vector<double> hs(nslots * ctx->total_items * S);
-  HIPC(hipMemcpy(hs.data(), ctx->d_pair_partial, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hs.data(), ctx->d_pair_partial.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> v(S);
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
@@ -1378,7 +1356,7 @@ int flush_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t, double* obs_
     if (herr) return kRcHandoffTimeout;
   }
   std::vector<double> h(nslots * ctx->total_items * 8);
-  HIPC(hipMemcpy(h.data(), ctx->d_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(h.data(), ctx->d_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
     if (P.side()) continue;  // the small-register engine writes its own sums
@@ -1408,7 +1386,7 @@ int flush_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t, double* obs_
   // the site sums of the same slots: tiles in order, a loopback group's members into shard 0's record
   const size_t S = (size_t)ctx->site_S;
   std::vector<double> hs(nslots * ctx->total_items * S);
-  HIPC(hipMemcpy(hs.data(), ctx->d_site_partial, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hs.data(), ctx->d_site_partial.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> v(S);
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
@@ -1556,7 +1534,7 @@ void dse_destroy(dse_ctx* ctx) {
   (void)sync_all(ctx);
   free_device(ctx);
   for (auto& p : ctx->probs) free_initial(p);
-  if (ctx->d_mx) (void)hipFree(ctx->d_mx), ctx->d_mx = nullptr;
+  ctx->d_mx.release();
   destroy_lanes(ctx);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
   delete ctx;
@@ -2039,13 +2017,13 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     P.final_bsel = 0;
   }
   {
-    int rc = upload_arena(ctx, arena, &ctx->d_sm_coef, &ctx->sm_coef_cap, ctx->small_stream);
+    int rc = upload_arena(ctx, arena, ctx->d_sm_coef, ctx->small_stream);
     if (rc) return rc;
   }
   for (int pi : sm) {
     HostProblem& P = ctx->probs[pi];
-    P.sm_coef = reinterpret_cast<double2*>(ctx->d_sm_coef + aoff[pi].first);
-    P.sm_deg = reinterpret_cast<int*>(ctx->d_sm_coef + aoff[pi].second);
+    P.sm_coef = reinterpret_cast<double2*>(ctx->d_sm_coef.p + aoff[pi].first);
+    P.sm_deg = reinterpret_cast<int*>(ctx->d_sm_coef.p + aoff[pi].second);
     desc[pi].coef = P.sm_coef;
     desc[pi].deg = P.sm_deg;
   }
@@ -2054,13 +2032,9 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   for (int pi : sm) extra += (size_t)ctx->probs[pi].n * ctx->probs[pi].n + 4 * (size_t)ctx->probs[pi].n;
   // aux ints: per register size the selection of problems, then the interval -> set map
   const size_t aux = ctx->probs.size() + (size_t)std::max(n_t - 1, 1) + 2 * extra + 64;
-  if (aux > ctx->small_aux_cap) {
-    if (ctx->d_small_aux) (void)hipFree(ctx->d_small_aux), ctx->d_small_aux = nullptr;
-    if (hipMalloc(&ctx->d_small_aux, aux * sizeof(int)) != hipSuccess) return fail(ctx, DSE_ERR_OOM, "small-engine allocation failed");
-    ctx->small_aux_cap = aux;
-  }
+  if (int rc = ctx->d_small_aux.reserve(ctx, aux, "small-engine allocation failed")) return rc;
   // tables after the ints (8-byte aligned)
-  double* tab = reinterpret_cast<double*>(ctx->d_small_aux + ((ctx->probs.size() + std::max(n_t - 1, 1) + 1) & ~size_t(1)));
+  double* tab = reinterpret_cast<double*>(ctx->d_small_aux.p + ((ctx->probs.size() + std::max(n_t - 1, 1) + 1) & ~size_t(1)));
   {
     std::vector<double> ht;
     ht.reserve(extra);
@@ -2084,40 +2058,20 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
       desc[pi].flip = tab + off[pi] + (size_t)ctx->probs[pi].n * ctx->probs[pi].n;
     }
   }
-  if (desc.size() > ctx->small_cap) {
-    if (ctx->d_small) (void)hipFree(ctx->d_small), ctx->d_small = nullptr;
-    if (hipMalloc(&ctx->d_small, desc.size() * sizeof(SmallProb)) != hipSuccess) return fail(ctx, DSE_ERR_OOM, "small-engine allocation failed");
-    ctx->small_cap = desc.size();
-  }
-  HIPC(hipMemcpy(ctx->d_small, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
+  if (int rc = ctx->d_small.reserve(ctx, desc.size(), "small-engine allocation failed")) return rc;
+  HIPC(hipMemcpy(ctx->d_small.p, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
   if (ctx->site_obs) {
     const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallSiteStride;
-    if (sn > ctx->small_sites_cap) {
-      if (ctx->d_small_sites) (void)hipFree(ctx->d_small_sites), ctx->d_small_sites = nullptr;
-      ctx->small_sites_cap = 0;
-      if (hipMalloc(&ctx->d_small_sites, sn * sizeof(double)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "small-engine site output allocation failed");
-      ctx->small_sites_cap = sn;
-    }
+    if (int rc = ctx->d_small_sites.reserve(ctx, sn, "small-engine site output allocation failed")) return rc;
   }
-  double* const d_sites = ctx->site_obs ? ctx->d_small_sites : nullptr;
+  double* const d_sites = ctx->site_obs ? ctx->d_small_sites.p : nullptr;
   if (ctx->pair_obs) {
     const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallPairStride;
-    if (sn > ctx->small_pairs_cap) {
-      if (ctx->d_small_pairs) (void)hipFree(ctx->d_small_pairs), ctx->d_small_pairs = nullptr;
-      ctx->small_pairs_cap = 0;
-      if (hipMalloc(&ctx->d_small_pairs, sn * sizeof(double)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "small-engine pair output allocation failed");
-      ctx->small_pairs_cap = sn;
-    }
+    if (int rc = ctx->d_small_pairs.reserve(ctx, sn, "small-engine pair output allocation failed")) return rc;
   }
-  double* const d_pairs = ctx->pair_obs ? ctx->d_small_pairs : nullptr;
+  double* const d_pairs = ctx->pair_obs ? ctx->d_small_pairs.p : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
-  if (outn > ctx->small_out_cap) {
-    if (ctx->d_small_out) (void)hipFree(ctx->d_small_out), ctx->d_small_out = nullptr;
-    if (hipMalloc(&ctx->d_small_out, outn * sizeof(double)) != hipSuccess) return fail(ctx, DSE_ERR_OOM, "small-engine output allocation failed");
-    ctx->small_out_cap = outn;
-  }
+  if (int rc = ctx->d_small_out.reserve(ctx, outn, "small-engine output allocation failed")) return rc;
   // selections per register size, then the interval -> set map
   std::vector<int> ints;
   std::vector<std::pair<int, std::pair<int, int>>> groups;  // n -> (offset, count)
@@ -2129,17 +2083,17 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   }
   const int iv_off = (int)ints.size();
   ints.insert(ints.end(), iv_set.begin(), iv_set.end());
-  HIPC(hipMemcpy(ctx->d_small_aux, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
+  HIPC(hipMemcpy(ctx->d_small_aux.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
-    HIPC(launch_small_obs0(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second,
-                           ctx->d_small_out, st, d_sites, d_pairs));
+    HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
+                           ctx->d_small_out.p, st, d_sites, d_pairs));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
-      HIPC(launch_small(g.first, ctx->d_small, ctx->d_small_aux + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux + iv_off, ctx->d_small_out, st, d_sites, d_pairs));
+      HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
+                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_sites, d_pairs));
       *launches += 1.0;
     }
   }
@@ -2152,7 +2106,7 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
   if (!any) return DSE_OK;
   HIPC(hipStreamSynchronize(ctx->small_stream));
   std::vector<double> h(ctx->probs.size() * (size_t)n_t * 8);
-  HIPC(hipMemcpy(h.data(), ctx->d_small_out, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(h.data(), ctx->d_small_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
     if (!P.sm) continue;
@@ -2162,7 +2116,7 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
   }
   if (ctx->pair_obs) {
     std::vector<double> hp(ctx->probs.size() * (size_t)n_t * kSmallPairStride);
-    HIPC(hipMemcpy(hp.data(), ctx->d_small_pairs, hp.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(hp.data(), ctx->d_small_pairs.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
       const HostProblem& P = ctx->probs[pi];
       if (!P.sm) continue;
@@ -2173,7 +2127,7 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
   }
   if (!ctx->site_obs) return DSE_OK;
   std::vector<double> hs(ctx->probs.size() * (size_t)n_t * kSmallSiteStride);
-  HIPC(hipMemcpy(hs.data(), ctx->d_small_sites, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hs.data(), ctx->d_small_sites.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
     if (!P.sm) continue;
@@ -2771,7 +2725,7 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
       mi *= std::complex<double>(0.0, -1.0);
     }
   }
-  // device buffers: kept in the context between calls (ctx->d_mx)
+  // device buffers: kept in the context between calls (ctx->d_mx.p)
   const size_t nb = dim / kSymvBlock;
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -2786,18 +2740,13 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
                oCoef = take(std::max(row.size() * sizeof(double2), cf.size() * sizeof(double))), oErr = take(sizeof(int)),
                oCnt = take(nb * sizeof(int));
   // option site_obs: the site sums of the same states, kept with the mode's other buffers (taken
-  // last and only with the option on: every other offset, and mx_cap with it off, as before)
+  // last and only with the option on: every other offset, and the size with it off, as before)
   const int sS = site_stride(n);
   const size_t oSites = ctx->site_obs ? take((size_t)n_t * sS * sizeof(double)) : 0;
   const int pS = pair_stride(n);  // option pair_obs: likewise
   const size_t oPairs = ctx->pair_obs ? take((size_t)n_t * pS * sizeof(double)) : 0;
-  if (off > ctx->mx_cap) {
-    if (ctx->d_mx) (void)hipFree(ctx->d_mx), ctx->d_mx = nullptr;
-    ctx->mx_cap = 0;
-    if (hipMalloc(&ctx->d_mx, off) != hipSuccess) return fail(ctx, DSE_ERR_OOM, "propagator-matrix mode: allocation failed");
-    ctx->mx_cap = off;
-  }
-  unsigned char* base = ctx->d_mx;
+  if (int rc = ctx->d_mx.reserve(ctx, off, "propagator-matrix mode: allocation failed")) return rc;
+  unsigned char* base = ctx->d_mx.p;
   double2* U = reinterpret_cast<double2*>(base + oU);     // tiles (real build) or columns: U e_c
   double2* S = reinterpret_cast<double2*>(base + oS);     // psi(t_j), consecutive
   double2* part = real_build ? reinterpret_cast<double2*>(base + oPart) : nullptr;
@@ -2998,11 +2947,11 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7) 
   int64_t off = 0;
   for (int i = 0; i < count; ++i) {
     HostProblem& P = ctx->probs[first + i];
-    HIPC(launch_obs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_partial + off * 8, st));
+    HIPC(launch_obs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_partial.p + off * 8, st));
     off += P.n_tiles;
   }
   std::vector<double> h(tiles * 8);
-  HIPC(hipMemcpyAsync(h.data(), ctx->d_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(h.data(), ctx->d_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
   double v[7] = {0, 0, 0, 0, 0, 0, 0};
   for (int64_t t = 0; t < tiles; ++t)
@@ -3037,12 +2986,12 @@ int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* o
   int64_t off = 0;
   for (int i = 0; i < count; ++i) {
     HostProblem& P = ctx->probs[first + i];
-    HIPC(launch_obs_sites(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_site_partial + off * S,
+    HIPC(launch_obs_sites(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_site_partial.p + off * S,
                           (int)S, st));
     off += P.n_tiles;
   }
   std::vector<double> h(tiles * S);
-  HIPC(hipMemcpyAsync(h.data(), ctx->d_site_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(h.data(), ctx->d_site_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
   const int n = ctx->probs[first].n;
   std::vector<double> v(S, 0.0);
@@ -3091,12 +3040,12 @@ int dse_pair_observables(dse_ctx* ctx, int problem, const double* psi, double* o
   int64_t off = 0;
   for (int i = 0; i < count; ++i) {
     HostProblem& P = ctx->probs[first + i];
-    HIPC(launch_obs_pairs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_pair_partial + off * S,
+    HIPC(launch_obs_pairs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_pair_partial.p + off * S,
                           (int)S, st));
     off += P.n_tiles;
   }
   std::vector<double> h(tiles * S);
-  HIPC(hipMemcpyAsync(h.data(), ctx->d_pair_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(h.data(), ctx->d_pair_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
   const int n = ctx->probs[first].n;
   const int nv = 5 * (n * (n - 1) / 2);
@@ -3284,266 +3233,340 @@ int build_real_table(const HostProblem& P, RealTab& T) {
   return DSE_OK;
 }
 
-static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_out, dse_stats* stats) {
-  const auto wall0 = std::chrono::steady_clock::now();
+}  // extern "C"
+
+namespace {
+
+// ---- dse_evolve: the plan of one call and the phases that fill and run it ----------------------
+
+struct IntervalGroup { int m0, n_out, set; };  // up to M consecutive output intervals: one launch per lane group
+
+// Kernel timing of the launch loop (option time_every): per lane and event pool the counters of the
+// launches under an event pair, and the sums drain() adds them to once the events have completed
+struct LaunchTimer {
+  // of one launch: algorithmic flops, HBM bytes (streaming; the persistent kernels' traffic is not
+  // modelled: 0) and amplitudes x Chebyshev terms
+  struct Rec { double flops, bytes, amp_terms; };
+  std::vector<std::vector<Rec>> recs;  // [lane * 2 + pool][event pair]
+  double step_ms = 0.0, launches = 0.0, flops = 0.0, bytes = 0.0, amp_terms = 0.0;
+  double lane0_ms = 0.0, lane0_launches = 0.0, lane0_amp_terms = 0.0;  // lane 0 alone (stats)
+
+  // launch() between two event records when the interval is timed and the pool has a pair left
+  // (records beyond the pool are skipped, not timed), bare otherwise
+  template <class F>
+  int run(dse_ctx* ctx, Lane& ln, size_t li, int pool, bool timed, const Rec& r, F&& launch) {
+    if (!timed || 2 * ln.ev_used[pool] + 2 > ln.ev[pool].size()) return launch();
+    const size_t i = ln.ev_used[pool]++;
+    HIPC(hipEventRecord(ln.ev[pool][2 * i], ln.stream));
+    if (int rc = launch()) return rc;
+    HIPC(hipEventRecord(ln.ev[pool][2 * i + 1], ln.stream));
+    recs[li * 2 + pool].push_back(r);
+    return DSE_OK;
+  }
+  int drain(dse_ctx* ctx, Lane& ln, size_t li, int pool) {
+    if (ln.ev_used[pool] == 0) return DSE_OK;
+    HIPC(hipEventSynchronize(ln.ev[pool][2 * ln.ev_used[pool] - 1]));
+    for (size_t i = 0; i < ln.ev_used[pool]; ++i) {
+      float ms = 0.f;
+      HIPC(hipEventElapsedTime(&ms, ln.ev[pool][2 * i], ln.ev[pool][2 * i + 1]));
+      const Rec& r = recs[li * 2 + pool][i];
+      step_ms += ms;
+      flops += r.flops;
+      amp_terms += r.amp_terms;
+      if (li == 0) lane0_ms += ms, lane0_amp_terms += r.amp_terms, lane0_launches += 1.0;
+      bytes += r.bytes;
+    }
+    launches += (double)ln.ev_used[pool];
+    ln.ev_used[pool] = 0;
+    recs[li * 2 + pool].clear();
+    return DSE_OK;
+  }
+};
+
+// What the phases of one dse_evolve decide and count; a phase reads another's results here or in ctx
+struct EvolvePlan {
+  const double* t = nullptr;  // the call's arguments
+  int n_t = 0;
+  double tol = 0.0, *obs_out = nullptr;
+  std::chrono::steady_clock::time_point wall0, tmark;
+  bool persistent = false, any_small = false, any_big = false, any_dense = false, any_dist = false;
+  bool any_dist_step = false;  // dist shards on the step kernels: per-term shard exchange
+  bool used_wht = false, all_span = true, imag_all = true;
+  bool obs_ovl = false;  // persistent with option obs_overlap
+  int matrix_pi = -1;    // the register in propagator-matrix mode (matrix_run), or -1; its time step
+  double matrix_dt = 0.0;
+  int M = 1;  // outputs per launch
+  std::vector<IntervalGroup> groups;
+  std::vector<std::vector<double>> set_tau;  // per coefficient set: offsets t[m0 + j + 1] - t[m0], j < n_out
+  size_t chunk = 1;                          // output slots of the partial arenas per flush
+  int n_lanes = 1;
+  int64_t cap = 2;  // workgroups of one 2-tile interval launch (all resident at once), even
+  std::vector<int2> items, span_items, real_items;
+  int* d_err = nullptr;  // the hand-off error word (persistent)
+  int max_deg = 1;
+  size_t slot = 0, t_flushed = 0;  // the launch loop: arena slots in use; output times already flushed
+  std::vector<double> dist_raw;    // raw sums of the registers partitioned over processes
+  // counters (stats)
+  double small_happl = 0.0, small_launches = 0.0, dense_ms = 0.0, dense_eig_ms = 0.0, matrix_happl = 0.0;
+  double launches = 0.0, amp_updates = 0.0, all_bytes = 0.0, all_flops = 0.0;
+  LaunchTimer timer;
+
   // DSE_HOST_TIMING=1: host time of each phase of this call on stderr (diagnostics)
-  static const bool host_timing = std::getenv("DSE_HOST_TIMING") != nullptr;
-  auto tmark = wall0;
-  auto phase = [&](const char* name) {
+  void phase(const char* name) {
+    static const bool host_timing = std::getenv("DSE_HOST_TIMING") != nullptr;
     if (!host_timing) return;
     const auto now = std::chrono::steady_clock::now();
     std::fprintf(stderr, "[dse_evolve] %-12s %9.3f ms\n", name,
                  std::chrono::duration<double, std::milli>(now - tmark).count());
     tmark = now;
-  };
-  if (!t || !obs_out) return fail(ctx, DSE_ERR_ARG, "null pointer");
-  if (n_t < 1) return fail(ctx, DSE_ERR_ARG, "n_t must be >= 1");
-  if (!(tol > 0.0 && tol < 1e-2)) return fail(ctx, DSE_ERR_ARG, "tol must be in (0, 1e-2)");
-  for (int i = 0; i < n_t; ++i)
-    if (!std::isfinite(t[i])) return fail(ctx, DSE_ERR_ARG, "non-finite time");
-  for (int i = 1; i < n_t; ++i)
-    if (!(t[i] > t[i - 1])) return fail(ctx, DSE_ERR_ARG, "times must be strictly increasing");
-  HIPC(hipSetDevice(ctx->device));
-  // timing-event records of an earlier call that ended early (an error, or the hand-off timeout
-  // dse_evolve re-runs) are dropped: their per-launch counters lived in that call
-  for (auto& ln : ctx->lanes) ln.ev_used[0] = ln.ev_used[1] = 0;
-  int rc = prepare(ctx);
-  if (rc) return rc;
-  ctx->xbytes = 0.0;
-  ctx->xms = 0.0;
-  ctx->xev_used = 0;
+  }
+};
 
-  phase("prepare");
-  // ---- execution mode ----
-  // small registers (n <= 9): the one-wave engine (dse_small.hip) on its own stream, whatever the
-  // other problems run on.  Of the rest -- persistent: every problem fits one or two
-  // register-block tiles -> one k_interval launch per group of output intervals and lane;
-  // streaming: per-term kernels, one output per group.
+int check_times(dse_ctx* ctx, const EvolvePlan& pl) {
+  if (!pl.t || !pl.obs_out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  if (pl.n_t < 1) return fail(ctx, DSE_ERR_ARG, "n_t must be >= 1");
+  if (!(pl.tol > 0.0 && pl.tol < 1e-2)) return fail(ctx, DSE_ERR_ARG, "tol must be in (0, 1e-2)");
+  for (int i = 0; i < pl.n_t; ++i)
+    if (!std::isfinite(pl.t[i])) return fail(ctx, DSE_ERR_ARG, "non-finite time");
+  for (int i = 1; i < pl.n_t; ++i)
+    if (!(pl.t[i] > pl.t[i - 1])) return fail(ctx, DSE_ERR_ARG, "times must be strictly increasing");
+  return DSE_OK;
+}
+
+// ---- execution mode ----
+// small registers (n <= 9): the one-wave engine (dse_small.hip) on its own stream, whatever the
+// other problems run on.  Of the rest -- persistent: every problem fits one or two
+// register-block tiles -> one k_interval launch per group of output intervals and lane;
+// streaming: per-term kernels, one output per group.
+int choose_engines(dse_ctx* ctx, EvolvePlan& pl) {
+  int rc;
   // dense engine first (option "dense"): a register it takes is off every Chebyshev path
-  bool any_small = false, any_big = false, any_dense = false;
   for (auto& P : ctx->probs) {
-    P.dn = ctx->dense && dense_eligible(P) && (ctx->dense == 2 || dense_cheaper(P, t, n_t, ctx->eig_impl));
-    any_dense = any_dense || P.dn;
+    P.dn = ctx->dense && dense_eligible(P) && (ctx->dense == 2 || dense_cheaper(P, pl.t, pl.n_t, ctx->eig_impl));
+    pl.any_dense = pl.any_dense || P.dn;
   }
   for (auto& P : ctx->probs) {
     P.mx = false;
     P.sm = !P.dn && ctx->small && P.shard_bits == 0 && P.n_local <= kSmallMaxQubits;
-    any_small = any_small || P.sm;
+    pl.any_small = pl.any_small || P.sm;
   }
   // a context whose Chebyshev work is one register: propagator-matrix mode (matrix_run) when the
   // persistent kernel is allowed and the model prefers it
-  int matrix_pi = -1;
-  double matrix_dt = 0.0;
-  {
-    int n_cheb = 0, last = -1;
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
-      if (!ctx->probs[pi].side()) ++n_cheb, last = (int)pi;
-    if (n_cheb == 1 && ctx->matrix && ctx->persistent) {
-      HostProblem& P = ctx->probs[last];
-      // the matrix-mode buffers must fit 80% of the free memory (plus what the context already
-      // holds for them); otherwise the register stays on the per-interval kernels
-      size_t free_b = 0, total_b = 0;
-      HIPC(hipMemGetInfo(&free_b, &total_b));
-      const bool fits = matrix_bytes(P, n_t) <= 0.8 * (double)free_b + (double)ctx->mx_cap;
-      if (fits && matrix_eligible(P, t, n_t, &matrix_dt) &&
-          (ctx->matrix == 2 || matrix_cheaper(P, matrix_dt, n_t, ctx->n_cu))) {
-        P.mx = true;
-        matrix_pi = last;
-      }
+  int n_cheb = 0, last = -1;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
+    if (!ctx->probs[pi].side()) ++n_cheb, last = (int)pi;
+  if (n_cheb == 1 && ctx->matrix && ctx->persistent) {
+    HostProblem& P = ctx->probs[last];
+    // the matrix-mode buffers must fit 80% of the free memory (plus what the context already
+    // holds for them); otherwise the register stays on the per-interval kernels
+    size_t free_b = 0, total_b = 0;
+    HIPC(hipMemGetInfo(&free_b, &total_b));
+    const bool fits = matrix_bytes(P, pl.n_t) <= 0.8 * (double)free_b + (double)ctx->d_mx.cap;
+    if (fits && matrix_eligible(P, pl.t, pl.n_t, &pl.matrix_dt) &&
+        (ctx->matrix == 2 || matrix_cheaper(P, pl.matrix_dt, pl.n_t, ctx->n_cu))) {
+      P.mx = true;
+      pl.matrix_pi = last;
     }
   }
-  for (auto& P : ctx->probs) any_big = any_big || !P.side();
+  for (auto& P : ctx->probs) pl.any_big = pl.any_big || !P.side();
   if (ctx->site_obs)
     for (auto& P : ctx->probs)
       if (P.dist)
         return fail(ctx, DSE_ERR_ARG, "site_obs: not available for a register partitioned over processes "
                                       "(the all-reduce of the site sums is not implemented)");
   if (ctx->pair_obs && (rc = pair_refusal(ctx, "pair_obs"))) return rc;
-  reset_site_store(ctx, n_t);
-  reset_pair_store(ctx, n_t);
-  bool persistent = ctx->persistent != 0;
-  bool any_dist = false;
-  // spanning registers (options span / span_tile): every register that fits runs on k_span over
-  // 2^s tiles.  span_tile = -1 (default, auto): when the context's registers are few enough that
-  // all their 2^11-amplitude tiles fit the chip in at most two resident launches (one GPU's share
-  // of a 4- or 8-GPU strong split, a lone simulate_rare register), a shorter chain per register;
-  // otherwise none spans (kSpanAutoTiles)
-  {
-    int tile = ctx->span_tile;
-    // the all-span candidates kSpanAutoTiles[ti0, ti1): the smallest tile whose workgroups fit
-    auto all_span_tile = [&](int ti0, int ti1) {
-      int tl = 0;
-      for (int ti = ti0; ti < ti1 && tl == 0; ++ti) {
-        const int L = kSpanAutoTiles[ti][0], chunks = kSpanAutoTiles[ti][1];
-        int64_t wg = 0;
-        bool all = persistent && ctx->span == 0;
-        for (auto& P : ctx->probs) {
-          if (P.side()) continue;
-          const int s = P.n_local - L;
-          if (!span_eligible(ctx, P, s)) all = false;
-          wg += int64_t(1) << std::max(0, s);
-        }
-        int per_cu = 1;
-        if (ti > 0 && span_occupancy(L, span_rb_for(ctx, L), true, &per_cu) != hipSuccess) per_cu = 0;
-        if (all && wg > 0 && chunks <= ctx->span_chunks && wg <= (int64_t)chunks * per_cu * ctx->n_cu) tl = L;
-      }
-      return tl;
-    };
-    auto assign = [&]() {
-      for (auto& P : ctx->probs) {
-        const int s = tile > 0 ? P.n_local - tile : ctx->span;
-        P.span_s = (persistent && span_eligible(ctx, P, s)) ? s : 0;
-      }
-    };
-    // order: every register spanned in one resident launch; else the partial span below; else
-    // every register spanned in two resident launches (the partial form measured faster on the
-    // 4-GPU share, 151 against 167 ms, profiles/r06/span_partial_shards.jsonl)
-    if (tile < 0) tile = all_span_tile(0, 2);
-    assign();
-    // Partial span (option span_partial, round 6): when the registers do not all fit spanned (one
-    // GPU's share of a 2-GPU split: 96 registers), the ones with the longest predicted chains span
-    // over 2^11-amplitude tiles on a lane of their own while the rest stay on k_interval, as long
-    // as every workgroup of both launches fits the chip at once (each takes a CU: residency of
-    // every hand-off partner is guaranteed, whatever order the two streams' workgroups land in).
-    // Predicted chain of a register: its spectral half-width (degree per interval ~ alpha dt) times
-    // the measured term time of its kernel under load (kTermUs); applied when the longest chain
-    // shrinks by at least 10%.
-    bool partial = false;
-    if (ctx->span_tile < 0 && tile == 0 && ctx->span == 0 && persistent && ctx->span_partial &&
-        std::min<int>(ctx->n_streams, (int)ctx->probs.size()) >= 2) {
-      const int Lp = ctx->span_partial_tile;
-      // term time under load: k_interval 1-tile, 2-tile; k_span over 2^Lp-amplitude tiles
-      const double kTermUs[3] = {19.5, 24.0, Lp == 11 ? 14.0 : 11.0};
-      struct C {
-        double chain;
-        int pi, kind;  // kind 0 / 1: k_interval of 1 / 2 tiles, 2: spanned
-      };
-      std::vector<C> cs;
-      int64_t wg = 0;
-      bool ok = true;
-      for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-        const HostProblem& P = ctx->probs[pi];
-        if (P.side()) continue;
-        if (P.shard_bits != 0 || !(P.n_tiles == 1 || P.n_tiles == 2) || !interval_supported(P.L)) {
-          ok = false;  // (and kTermUs has entries for 1- and 2-tile registers only)
-          break;
-        }
-        wg += P.n_tiles;
-        const double alpha = 0.5 * (P.e_max - P.e_min);
-        cs.push_back({alpha * kTermUs[P.n_tiles - 1], (int)pi, (int)P.n_tiles - 1});
-      }
-      auto worst = [&]() { return std::max_element(cs.begin(), cs.end(), [](const C& a, const C& b) { return a.chain < b.chain; }); };
-      if (ok && !cs.empty() && wg <= ctx->n_cu) {
-        const double before = worst()->chain;
-        std::vector<int> spanned;
-        for (;;) {
-          auto w = worst();
-          if (w->kind == 2) break;
-          const HostProblem& P = ctx->probs[w->pi];
-          const int sp = P.n_local - Lp;
-          if (!span_eligible(ctx, P, sp)) break;
-          const int64_t extra = (int64_t(1) << sp) - P.n_tiles;
-          if (wg + extra > ctx->n_cu) break;
-          wg += extra;
-          w->chain = w->chain / kTermUs[w->kind] * kTermUs[2];
-          w->kind = 2;
-          spanned.push_back(w->pi);
-        }
-        if (!spanned.empty() && worst()->chain <= 0.9 * before) {
-          for (int pi : spanned) ctx->probs[pi].span_s = ctx->probs[pi].n_local - Lp;
-          partial = true;
-        }
-      }
-    }
-    if (ctx->span_tile < 0 && tile == 0 && !partial && (tile = all_span_tile(2, 3)) > 0) assign();
-  }
-  for (auto& P : ctx->probs) {
-    if (P.side()) continue;
-    if (P.span_s == 0 && (!(interval_supported(P.L) && P.n_tiles <= 2) || P.shard_bits > 0)) persistent = false;
-    any_dist = any_dist || P.dist;
-  }
-  if (!persistent)
-    for (auto& P : ctx->probs) P.span_s = 0;
-  // real-component mode: option real = 1 when every Chebyshev register qualifies (one launch kind
-  // per interval); real = 2 the 2-tile (14-qubit) registers only, on their own stream beside the
-  // 1-tile registers' k_interval launches (neither kernel waits on another workgroup, so the two
-  // persistent launches share the chip without a residency condition)
-  {
-    bool real_mode = persistent && ctx->real_mode && !ctx->obs_overlap;
-    int n_cheb = 0;
+  reset_site_store(ctx, pl.n_t);
+  reset_pair_store(ctx, pl.n_t);
+  pl.persistent = ctx->persistent != 0;
+  return DSE_OK;
+}
+
+// the all-span candidates kSpanAutoTiles[ti0, ti1): the smallest tile whose workgroups fit (0: none)
+int all_span_tile(dse_ctx* ctx, bool persistent, int ti0, int ti1) {
+  int tl = 0;
+  for (int ti = ti0; ti < ti1 && tl == 0; ++ti) {
+    const int L = kSpanAutoTiles[ti][0], chunks = kSpanAutoTiles[ti][1];
+    int64_t wg = 0;
+    bool all = persistent && ctx->span == 0;
     for (auto& P : ctx->probs) {
       if (P.side()) continue;
-      ++n_cheb;
-      if (ctx->real_mode == 1) real_mode = real_mode && real_eligible(P);
+      const int s = P.n_local - L;
+      if (!span_eligible(ctx, P, s)) all = false;
+      wg += int64_t(1) << std::max(0, s);
     }
-    for (auto& P : ctx->probs)
-      P.rl = real_mode && n_cheb > 0 && !P.side() && (ctx->real_mode == 1 || (real_eligible(P) && P.n_tiles == 2));
+    int per_cu = 1;
+    if (ti > 0 && span_occupancy(L, span_rb_for(ctx, L), true, &per_cu) != hipSuccess) per_cu = 0;
+    if (all && wg > 0 && chunks <= ctx->span_chunks && wg <= (int64_t)chunks * per_cu * ctx->n_cu) tl = L;
   }
-  // streaming: registers of more than one 2^13 tile take the Walsh-Hadamard engine (option wht)
-  bool used_wht = false;
-  bool any_dist_step = any_dist;  // dist shards on the step kernels: per-term shard exchange
-  if (!persistent) {
-    if ((rc = ensure_wht(ctx))) return rc;
-    any_dist_step = false;
+  return tl;
+}
+
+// Partial span (option span_partial, round 6): when the registers do not all fit spanned (one
+// GPU's share of a 2-GPU split: 96 registers), the ones with the longest predicted chains span
+// over 2^11-amplitude tiles on a lane of their own while the rest stay on k_interval, as long
+// as every workgroup of both launches fits the chip at once (each takes a CU: residency of
+// every hand-off partner is guaranteed, whatever order the two streams' workgroups land in).
+// Predicted chain of a register: its spectral half-width (degree per interval ~ alpha dt) times
+// the measured term time of its kernel under load (kTermUs); applied when the longest chain
+// shrinks by at least 10%.  True when it set the span_s of some registers.
+bool choose_partial_span(dse_ctx* ctx) {
+  if (ctx->span != 0 || !ctx->span_partial || std::min<int>(ctx->n_streams, (int)ctx->probs.size()) < 2) return false;
+  const int Lp = ctx->span_partial_tile;
+  // term time under load: k_interval 1-tile, 2-tile; k_span over 2^Lp-amplitude tiles
+  const double kTermUs[3] = {19.5, 24.0, Lp == 11 ? 14.0 : 11.0};
+  struct C {
+    double chain;
+    int pi, kind;  // kind 0 / 1: k_interval of 1 / 2 tiles, 2: spanned
+  };
+  std::vector<C> cs;
+  int64_t wg = 0;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    if (P.side()) continue;
+    // (and kTermUs has entries for 1- and 2-tile registers only)
+    if (P.shard_bits != 0 || !(P.n_tiles == 1 || P.n_tiles == 2) || !interval_supported(P.L)) return false;
+    wg += P.n_tiles;
+    const double alpha = 0.5 * (P.e_max - P.e_min);
+    cs.push_back({alpha * kTermUs[P.n_tiles - 1], (int)pi, (int)P.n_tiles - 1});
+  }
+  auto worst = [&]() { return std::max_element(cs.begin(), cs.end(), [](const C& a, const C& b) { return a.chain < b.chain; }); };
+  if (cs.empty() || wg > ctx->n_cu) return false;
+  const double before = worst()->chain;
+  std::vector<int> spanned;
+  for (;;) {
+    auto w = worst();
+    if (w->kind == 2) break;
+    const HostProblem& P = ctx->probs[w->pi];
+    const int sp = P.n_local - Lp;
+    if (!span_eligible(ctx, P, sp)) break;
+    const int64_t extra = (int64_t(1) << sp) - P.n_tiles;
+    if (wg + extra > ctx->n_cu) break;
+    wg += extra;
+    w->chain = w->chain / kTermUs[w->kind] * kTermUs[2];
+    w->kind = 2;
+    spanned.push_back(w->pi);
+  }
+  if (spanned.empty() || worst()->chain > 0.9 * before) return false;
+  for (int pi : spanned) ctx->probs[pi].span_s = ctx->probs[pi].n_local - Lp;
+  return true;
+}
+
+// spanning registers (options span / span_tile): every register that fits runs on k_span over
+// 2^s tiles.  span_tile = -1 (default, auto): when the context's registers are few enough that
+// all their 2^11-amplitude tiles fit the chip in at most two resident launches (one GPU's share
+// of a 4- or 8-GPU strong split, a lone simulate_rare register), a shorter chain per register;
+// otherwise none spans (kSpanAutoTiles).  Then whether the evolve is persistent at all.
+void choose_span(dse_ctx* ctx, EvolvePlan& pl) {
+  const bool persistent = pl.persistent;
+  int tile = ctx->span_tile;
+  auto assign = [&]() {
     for (auto& P : ctx->probs) {
-      used_wht = used_wht || P.wht_groups > 0;
-      any_dist_step = any_dist_step || (P.dist && P.wht_groups == 0);
+      const int s = tile > 0 ? P.n_local - tile : ctx->span;
+      P.span_s = (persistent && span_eligible(ctx, P, s)) ? s : 0;
     }
+  };
+  // order: every register spanned in one resident launch; else the partial span; else every
+  // register spanned in two resident launches (the partial form measured faster on the 4-GPU
+  // share, 151 against 167 ms, profiles/r06/span_partial_shards.jsonl)
+  if (tile < 0) tile = all_span_tile(ctx, persistent, 0, 2);
+  assign();
+  const bool automatic = ctx->span_tile < 0 && tile == 0;
+  const bool partial = automatic && persistent && choose_partial_span(ctx);
+  if (automatic && !partial && (tile = all_span_tile(ctx, persistent, 2, 3)) > 0) assign();
+  for (auto& P : ctx->probs) {
+    if (P.side()) continue;
+    if (P.span_s == 0 && (!(interval_supported(P.L) && P.n_tiles <= 2) || P.shard_bits > 0)) pl.persistent = false;
+    pl.any_dist = pl.any_dist || P.dist;
   }
-  // Outputs per launch M: the Chebyshev series of e^{-iH tau} converges after ~ alpha tau +
-  // O((alpha tau)^{1/3}) terms, so M outputs from one series (one propagator sum per output, same
-  // vectors T_k(H~) psi) need fewer H applications than M series of one interval each when alpha
-  // dt is small (the N = 14 sweep on its 1 ms grid: -23% for the stiffest problem at M = 4).  On
-  // coarse grids (alpha dt >= 400) the saving is nil and the coefficient tables grow, so M = 1.
+  if (!pl.persistent)
+    for (auto& P : ctx->probs) P.span_s = 0;
+}
+
+// real-component mode: option real = 1 when every Chebyshev register qualifies (one launch kind
+// per interval); real = 2 the 2-tile (14-qubit) registers only, on their own stream beside the
+// 1-tile registers' k_interval launches (neither kernel waits on another workgroup, so the two
+// persistent launches share the chip without a residency condition)
+void choose_real(dse_ctx* ctx, const EvolvePlan& pl) {
+  bool real_mode = pl.persistent && ctx->real_mode && !ctx->obs_overlap;
+  int n_cheb = 0;
+  for (auto& P : ctx->probs) {
+    if (P.side()) continue;
+    ++n_cheb;
+    if (ctx->real_mode == 1) real_mode = real_mode && real_eligible(P);
+  }
+  for (auto& P : ctx->probs)
+    P.rl = real_mode && n_cheb > 0 && !P.side() && (ctx->real_mode == 1 || (real_eligible(P) && P.n_tiles == 2));
+}
+
+// streaming: registers of more than one 2^13 tile take the Walsh-Hadamard engine (option wht)
+int choose_wht(dse_ctx* ctx, EvolvePlan& pl) {
+  pl.any_dist_step = pl.any_dist;
+  if (pl.persistent) return DSE_OK;
+  if (int rc = ensure_wht(ctx)) return rc;
+  pl.any_dist_step = false;
+  for (auto& P : ctx->probs) {
+    pl.used_wht = pl.used_wht || P.wht_groups > 0;
+    pl.any_dist_step = pl.any_dist_step || (P.dist && P.wht_groups == 0);
+  }
+  return DSE_OK;
+}
+
+// Outputs per launch M: the Chebyshev series of e^{-iH tau} converges after ~ alpha tau +
+// O((alpha tau)^{1/3}) terms, so M outputs from one series (one propagator sum per output, same
+// vectors T_k(H~) psi) need fewer H applications than M series of one interval each when alpha
+// dt is small (the N = 14 sweep on its 1 ms grid: -23% for the stiffest problem at M = 4).  On
+// coarse grids (alpha dt >= 400) the saving is nil and the coefficient tables grow, so M = 1.
+void choose_outputs_per_launch(dse_ctx* ctx, EvolvePlan& pl) {
   double max_z = 0.0;
-  for (int m = 0; m + 1 < n_t; ++m)
+  for (int m = 0; m + 1 < pl.n_t; ++m)
     for (auto& P : ctx->probs)
-      if (!P.side()) max_z = std::max(max_z, 0.5 * (P.e_max - P.e_min) * (t[m + 1] - t[m]));
+      if (!P.side()) max_z = std::max(max_z, 0.5 * (P.e_max - P.e_min) * (pl.t[m + 1] - pl.t[m]));
   // k_span staggers its outputs' sums over the terms (coef_nterm phases), so an evolve whose
   // registers all span takes up to kSpanMaxOut outputs per series (option span_outputs);
   // k_interval and k_real update every output's sum in one term, from registers: at most two
-  bool all_span = true;
   for (auto& P : ctx->probs)
-    if (!P.side()) all_span = all_span && P.span_s > 0 && !P.rl;
-  int M = 1;
-  if (persistent && max_z < 400.0)
-    M = std::max(1, std::min(all_span ? ctx->span_outputs : ctx->outputs_per_launch, n_t - 1));
+    if (!P.side()) pl.all_span = pl.all_span && P.span_s > 0 && !P.rl;
+  if (pl.persistent && max_z < 400.0)
+    pl.M = std::max(1, std::min(pl.all_span ? ctx->span_outputs : ctx->outputs_per_launch, pl.n_t - 1));
+  pl.obs_ovl = pl.persistent && ctx->obs_overlap;
+}
 
-  // ---- groups of M consecutive output intervals -> coefficient sets (distinct offset lists) ----
-  struct Group {
-    int m0, n_out, set;
-  };
-  std::vector<Group> groups;
-  std::vector<std::vector<double>> set_tau;  // offsets t[m0 + j + 1] - t[m0], j < n_out
+// groups of M consecutive output intervals -> coefficient sets (distinct offset lists)
+int group_intervals(dse_ctx* ctx, EvolvePlan& pl) {
+  const double* t = pl.t;
+  const int n_t = pl.n_t, M = pl.M;
   for (int m0 = 0; m0 + 1 < n_t; m0 += M) {
-    Group g;
+    IntervalGroup g;
     g.m0 = m0;
     g.n_out = std::min(M, n_t - 1 - m0);
     std::vector<double> tau(g.n_out);
     for (int j = 0; j < g.n_out; ++j) tau[j] = t[m0 + j + 1] - t[m0];
     g.set = -1;
-    for (size_t q = 0; q < set_tau.size(); ++q)
-      if (set_tau[q] == tau) {
+    for (size_t q = 0; q < pl.set_tau.size(); ++q)
+      if (pl.set_tau[q] == tau) {
         g.set = (int)q;
         break;
       }
     if (g.set < 0) {
-      if (set_tau.size() >= 4096) return fail(ctx, DSE_ERR_ARG, "more than 4096 distinct output intervals");
-      g.set = (int)set_tau.size();
-      set_tau.push_back(tau);
+      if (pl.set_tau.size() >= 4096) return fail(ctx, DSE_ERR_ARG, "more than 4096 distinct output intervals");
+      g.set = (int)pl.set_tau.size();
+      pl.set_tau.push_back(tau);
     }
-    groups.push_back(g);
+    pl.groups.push_back(g);
   }
-  if (set_tau.empty()) set_tau.push_back(std::vector<double>(1, 0.0));
-  const int n_sets = (int)set_tau.size();
-  const int n_groups = (int)groups.size();
+  if (pl.set_tau.empty()) pl.set_tau.push_back(std::vector<double>(1, 0.0));
+  return DSE_OK;
+}
 
-  phase("groups");
-  // ---- Chebyshev coefficients per problem: rows [set][output j][term k], all problems' rows
-  // gathered into one arena and uploaded with one copy ----
-  // Problems are independent: computed on up to 16 host threads (Bessel series of every distinct
-  // offset set, ~3 us each), then gathered in problem order.
-  std::vector<std::vector<double2>> coef_rows(ctx->probs.size());
+// Chebyshev coefficients per problem (cheb_rows: [set][output j][term k]), all problems' rows
+// gathered into one arena and uploaded with one copy.  Problems are independent: computed on up to
+// 16 host threads (Bessel series of every distinct offset set, ~3 us each), then gathered in
+// problem order.
+int build_coefficients(dse_ctx* ctx, EvolvePlan& pl) {
+  using Row = std::pair<double, double>;
+  static_assert(sizeof(Row) == sizeof(double2), "cheb_rows fills the device's double2 rows");
+  const int M = pl.M;
+  std::vector<std::vector<Row>> coef_rows(ctx->probs.size());
   std::vector<int> coef_rc(ctx->probs.size(), DSE_OK);
   std::vector<std::string> coef_msg(ctx->probs.size());
   auto coef_one = [&](size_t pi) {
@@ -3551,56 +3574,21 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     if (P.side()) return;
     const double alpha = std::max(0.5 * (P.e_max - P.e_min), 1e-300);
     const double beta = 0.5 * (P.e_max + P.e_min);
-    int deg = 1;
-    std::vector<std::vector<double>> J((size_t)n_sets * M);
-    std::vector<int> deg_sj((size_t)n_sets * M, 0);
-    for (int s = 0; s < n_sets; ++s)
-      for (size_t j = 0; j < set_tau[s].size(); ++j) {
-        const double z = alpha * set_tau[s][j];
-        const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
-        if (kmax > ctx->max_degree) {
-          coef_rc[pi] = DSE_ERR_CONVERGENCE;
-          coef_msg[pi] = "Chebyshev degree " + std::to_string(kmax) + " exceeds max_degree; use a finer output grid";
-          return;
-        }
-        std::vector<double>& Jv = J[(size_t)s * M + j];
-        Jv.resize(kmax + 1);
-        int d = 1;
-        if (dse_bessel_j(z, kmax, Jv.data(), tol, &d) != DSE_OK) {
-          coef_rc[pi] = DSE_ERR_ARG;
-          coef_msg[pi] = "bessel failed";
-          return;
-        }
-        deg_sj[(size_t)s * M + j] = d;
-        deg = std::max(deg, d);
-      }
+    int deg = 1, kmax = 0;
+    coef_rc[pi] = cheb_rows(alpha, beta, pl.set_tau, M, pl.tol, ctx->max_degree, &deg, &coef_rows[pi], &kmax);
+    if (coef_rc[pi] == DSE_ERR_CONVERGENCE)
+      coef_msg[pi] = "Chebyshev degree " + std::to_string(kmax) + " exceeds max_degree; use a finer output grid";
+    else if (coef_rc[pi] != DSE_OK)
+      coef_msg[pi] = "bessel failed";
+    if (coef_rc[pi] != DSE_OK) return;
     P.degree = deg;
-    const int kcap1 = deg + 1;
-    // compact rows (coef_row): [set][j] x (kcap1 + 1) entries, [0].x = degree, [1 + k] = a_k
-    std::vector<double2>& coef = coef_rows[pi];
-    coef.assign((size_t)n_sets * M * (kcap1 + 1), make_double2(0.0, 0.0));
-    for (int s = 0; s < n_sets; ++s)
-      for (size_t j = 0; j < set_tau[s].size(); ++j) {
-        const std::vector<double>& Jv = J[(size_t)s * M + j];
-        const int dj = deg_sj[(size_t)s * M + j];
-        const double ph = -beta * set_tau[s][j];
-        const std::complex<double> e(std::cos(ph), std::sin(ph));
-        std::complex<double> mi(1.0, 0.0);  // (-i)^k
-        double2* row = coef.data() + ((size_t)s * M + j) * (kcap1 + 1);
-        row[0] = make_double2((double)dj, 0.0);
-        for (int k = 0; k <= dj; ++k) {
-          const std::complex<double> a = e * mi * ((k == 0 ? 1.0 : 2.0) * Jv[k]);
-          row[1 + k] = make_double2(a.real(), a.imag());
-          mi *= std::complex<double>(0.0, -1.0);
-        }
-      }
     DevProb& d = ctx->h_desc[pi];
-    d.kcap1 = kcap1;
+    d.kcap1 = deg + 1;
     d.degree = deg;
     d.beta = beta;
     d.s1 = 1.0 / alpha;
     d.n_acc = M;
-    d.xacc_q = (persistent && ctx->obs_overlap) ? M - 1 : 0;
+    d.xacc_q = pl.obs_ovl ? M - 1 : 0;
   };
   if (ctx->dbg & 4)
     for (size_t pi = 0; pi < ctx->probs.size(); ++pi) coef_one(pi);
@@ -3611,112 +3599,91 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   size_t coef_total = 0;
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     if (coef_rc[pi] != DSE_OK) return fail(ctx, coef_rc[pi], coef_msg[pi]);
-    coef_total += align_up(coef_rows[pi].size() * sizeof(double2), 64);
+    coef_total += align_up(coef_rows[pi].size() * sizeof(Row), 64);
   }
   coef_arena.host.reserve(coef_total);
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
-    if (!ctx->probs[pi].side()) coef_off[pi] = coef_arena.place(coef_rows[pi].size() * sizeof(double2));
+    if (!ctx->probs[pi].side()) coef_off[pi] = coef_arena.place(coef_rows[pi].size() * sizeof(Row));
   parallel_for(ctx->probs.size(), [&](size_t pi) {
     if (!coef_rows[pi].empty())
-      std::memcpy(coef_arena.host.data() + coef_off[pi], coef_rows[pi].data(), coef_rows[pi].size() * sizeof(double2));
+      std::memcpy(coef_arena.host.data() + coef_off[pi], coef_rows[pi].data(), coef_rows[pi].size() * sizeof(Row));
   });
 
-  phase("coefficients");
-  if ((rc = upload_arena(ctx, coef_arena, &ctx->d_coef, &ctx->coef_cap, ctx->lanes[0].stream))) return rc;
+  pl.phase("coefficients");
+  if (int rc = upload_arena(ctx, coef_arena, ctx->d_coef, ctx->lanes[0].stream)) return rc;
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     HostProblem& P = ctx->probs[pi];
     if (P.side()) continue;
-    P.coef = reinterpret_cast<double2*>(ctx->d_coef + coef_off[pi]);
+    P.coef = reinterpret_cast<double2*>(ctx->d_coef.p + coef_off[pi]);
     ctx->h_desc[pi].coef = P.coef;
   }
+  pl.phase("coef upload");
+  return DSE_OK;
+}
 
-  phase("coef upload");
+int place_output_buffers(dse_ctx* ctx, const EvolvePlan& pl) {
+  const int M = pl.M;
+  int rc;
   // intermediate outputs of multi-output launches: (M - 1) state vectors per problem, two sets
   // (one per launch parity) when the observables are overlapped
-  const bool obs_ovl = persistent && ctx->obs_overlap;
-  {
-    const size_t xsets = obs_ovl ? 2 : 1;
-    size_t need = 0;
-    if (M > 1)
-      for (auto& P : ctx->probs)
-        if (!P.side()) need += xsets * ((size_t)(M - 1) << P.n_local);
-    if (need > ctx->xacc_cap) {
-      if (ctx->d_xacc) (void)hipFree(ctx->d_xacc), ctx->d_xacc = nullptr;
-      ctx->xacc_cap = 0;
-      if (hipMalloc(&ctx->d_xacc, need * sizeof(double2)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "output accumulator allocation failed (" +
-                                          std::to_string(need * sizeof(double2)) + " bytes)");
-      ctx->xacc_cap = need;
-    }
-    size_t off = 0;
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-      const bool use = M > 1 && !ctx->probs[pi].side();
-      ctx->h_desc[pi].xacc = use ? ctx->d_xacc + off : nullptr;
-      if (use) off += xsets * ((size_t)(M - 1) << ctx->probs[pi].n_local);
-    }
+  const size_t xsets = pl.obs_ovl ? 2 : 1;
+  size_t xneed = 0, xoff = 0;
+  if (M > 1)
+    for (auto& P : ctx->probs)
+      if (!P.side()) xneed += xsets * ((size_t)(M - 1) << P.n_local);
+  if ((rc = ctx->d_xacc.reserve(ctx, xneed, "output accumulator allocation failed", true))) return rc;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const bool use = M > 1 && !ctx->probs[pi].side();
+    ctx->h_desc[pi].xacc = use ? ctx->d_xacc.p + xoff : nullptr;
+    if (use) xoff += xsets * ((size_t)(M - 1) << ctx->probs[pi].n_local);
   }
   // real-component registers: tables, [a | b] inputs and per-output, per-component sums
-  {
-    Arena tabs;
-    std::vector<size_t> tab_off(ctx->probs.size(), 0);
-    size_t need = 0;  // in double2 units
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-      const HostProblem& P = ctx->probs[pi];
-      ctx->h_desc[pi].rtab = nullptr;
-      ctx->h_desc[pi].rin = nullptr;
-      ctx->h_desc[pi].racc = nullptr;
-      if (!P.rl) continue;
-      RealTab T;
-      if ((rc = build_real_table(P, T)) != DSE_OK) return fail(ctx, rc, "real-mode tables: drives not imaginary");
-      tab_off[pi] = tabs.add(&T, sizeof(T));
-      need += ((size_t)1 + 2 * (size_t)M) << P.n_local;
-    }
-    if (need > 0) {
-      if ((rc = upload_arena(ctx, tabs, &ctx->d_real_tab, &ctx->real_tab_cap, ctx->lanes[0].stream))) return rc;
-      HIPC(hipStreamSynchronize(ctx->lanes[0].stream));
-      if (need * sizeof(double2) > ctx->real_cap) {
-        if (ctx->d_real) (void)hipFree(ctx->d_real), ctx->d_real = nullptr;
-        ctx->real_cap = 0;
-        if (hipMalloc(&ctx->d_real, need * sizeof(double2)) != hipSuccess)
-          return fail(ctx, DSE_ERR_OOM, "real-mode buffer allocation failed (" +
-                                            std::to_string(need * sizeof(double2)) + " bytes)");
-        ctx->real_cap = need * sizeof(double2);
-      }
-      double2* base = reinterpret_cast<double2*>(ctx->d_real);
-      size_t off = 0;
-      for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-        const HostProblem& P = ctx->probs[pi];
-        if (!P.rl) continue;
-        DevProb& d = ctx->h_desc[pi];
-        d.rtab = reinterpret_cast<const RealTab*>(ctx->d_real_tab + tab_off[pi]);
-        d.rin = reinterpret_cast<double*>(base + off);  // [a | b]: 2 x 2^n doubles
-        d.racc = base + off + ((size_t)1 << P.n_local);
-        off += ((size_t)1 + 2 * (size_t)M) << P.n_local;
-      }
-    }
+  Arena tabs;
+  std::vector<size_t> tab_off(ctx->probs.size(), 0);
+  size_t need = 0;  // in double2 units
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    ctx->h_desc[pi].rtab = nullptr;
+    ctx->h_desc[pi].rin = nullptr;
+    ctx->h_desc[pi].racc = nullptr;
+    if (!P.rl) continue;
+    RealTab T;
+    if ((rc = build_real_table(P, T)) != DSE_OK) return fail(ctx, rc, "real-mode tables: drives not imaginary");
+    tab_off[pi] = tabs.add(&T, sizeof(T));
+    need += ((size_t)1 + 2 * (size_t)M) << P.n_local;
   }
+  if (need == 0) return DSE_OK;
+  if ((rc = upload_arena(ctx, tabs, ctx->d_real_tab, ctx->lanes[0].stream))) return rc;
+  HIPC(hipStreamSynchronize(ctx->lanes[0].stream));
+  if ((rc = ctx->d_real.reserve(ctx, need, "real-mode buffer allocation failed", true))) return rc;
+  size_t off = 0;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    if (!P.rl) continue;
+    DevProb& d = ctx->h_desc[pi];
+    d.rtab = reinterpret_cast<const RealTab*>(ctx->d_real_tab.p + tab_off[pi]);
+    d.rin = reinterpret_cast<double*>(ctx->d_real.p + off);  // [a | b]: 2 x 2^n doubles
+    d.racc = ctx->d_real.p + off + ((size_t)1 << P.n_local);
+    off += ((size_t)1 + 2 * (size_t)M) << P.n_local;
+  }
+  return DSE_OK;
+}
 
-  // ---- lanes ----
-  // persistent: 2-tile problems on lane 0 (their workgroup pairs must be co-resident), 1-tile
-  // problems on lane 1.  streaming: problems by degree dealt round-robin over the lanes.
-  if (persistent) {
+// persistent: the hand-off slots of the 2-tile problems and the spanning registers' tables,
+// descriptors, slots and flags; then the problem descriptors, complete, to the device
+int place_handoff_buffers(dse_ctx* ctx, const EvolvePlan& pl) {
+  int rc;
+  if (pl.persistent) {
     // hand-off slots of the 2-tile problems: [2 tiles][kXSlots][2^L] amplitudes each
     // (dse_interval.hip)
     size_t need = 0;
     for (auto& P : ctx->probs)
       if (P.n_tiles == 2) need += (size_t)2 * kXSlots << P.L;
-    if (need > ctx->xslot_cap) {
-      if (ctx->d_xslots) (void)hipFree(ctx->d_xslots), ctx->d_xslots = nullptr;
-      ctx->xslot_cap = 0;
-      if (hipMalloc(&ctx->d_xslots, need * sizeof(double2)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "hand-off slot allocation failed (" +
-                                          std::to_string(need * sizeof(double2)) + " bytes)");
-      ctx->xslot_cap = need;
-    }
+    if ((rc = ctx->d_xslots.reserve(ctx, need, "hand-off slot allocation failed", true))) return rc;
     size_t off = 0;
     for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
       const HostProblem& P = ctx->probs[pi];
-      ctx->h_desc[pi].xslots = P.n_tiles == 2 ? ctx->d_xslots + off : nullptr;
+      ctx->h_desc[pi].xslots = P.n_tiles == 2 ? ctx->d_xslots.p + off : nullptr;
       if (P.n_tiles == 2) off += (size_t)2 * kXSlots << P.L;
     }
     // spanning registers: tables (one arena), descriptors, hand-off slots and flags
@@ -3735,58 +3702,96 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
       flag_need += (size_t)kSpanWaves << P.span_s;
     }
     if (flag_need > 0) {
-      if ((rc = upload_arena(ctx, tabs, &ctx->d_span_tab, &ctx->span_tab_cap, ctx->lanes[0].stream))) return rc;
+      if ((rc = upload_arena(ctx, tabs, ctx->d_span_tab, ctx->lanes[0].stream))) return rc;
       HIPC(hipStreamSynchronize(ctx->lanes[0].stream));
-      auto grow = [&](auto** ptr, size_t* cap, size_t need_bytes, const char* what) -> int {
-        if (need_bytes <= *cap) return DSE_OK;
-        if (*ptr) (void)hipFree(*ptr), *ptr = nullptr;
-        *cap = 0;
-        if (hipMalloc(ptr, need_bytes) != hipSuccess)
-          return fail(ctx, DSE_ERR_OOM, std::string(what) + " allocation failed (" + std::to_string(need_bytes) + " bytes)");
-        *cap = need_bytes;
-        return DSE_OK;
-      };
-      if ((rc = grow(&ctx->d_span_slots, &ctx->span_slot_cap, slot_need * sizeof(double2), "span slot"))) return rc;
-      if ((rc = grow(&ctx->d_span_flags, &ctx->span_flag_cap, flag_need * sizeof(int), "span flag"))) return rc;
-      if ((rc = grow(&ctx->d_span, &ctx->span_cap, ctx->probs.size() * sizeof(SpanDesc), "span descriptor"))) return rc;
+      if ((rc = ctx->d_span_slots.reserve(ctx, slot_need, "span slot allocation failed", true))) return rc;
+      if ((rc = ctx->d_span_flags.reserve(ctx, flag_need, "span flag allocation failed", true))) return rc;
+      if ((rc = ctx->d_span.reserve(ctx, ctx->probs.size(), "span descriptor allocation failed", true))) return rc;
       std::vector<SpanDesc> sd(ctx->probs.size());
       size_t so = 0, fo = 0;
       for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
         const HostProblem& P = ctx->probs[pi];
         std::memset(&sd[pi], 0, sizeof(SpanDesc));
         if (!P.span_s) continue;
-        sd[pi].tab = reinterpret_cast<const SpanTab*>(ctx->d_span_tab + tab_off[pi]);
-        sd[pi].slots = ctx->d_span_slots + so;
-        sd[pi].flags = ctx->d_span_flags + fo;
+        sd[pi].tab = reinterpret_cast<const SpanTab*>(ctx->d_span_tab.p + tab_off[pi]);
+        sd[pi].slots = ctx->d_span_slots.p + so;
+        sd[pi].flags = ctx->d_span_flags.p + fo;
         sd[pi].s = P.span_s;
         sd[pi].L = P.n_local - P.span_s;
         so += (size_t)(P.span_s + 1) * kXSlots << P.n_local;
         fo += (size_t)kSpanWaves << P.span_s;
       }
-      HIPC(hipMemcpy(ctx->d_span, sd.data(), sd.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
+      HIPC(hipMemcpy(ctx->d_span.p, sd.data(), sd.size() * sizeof(SpanDesc), hipMemcpyHostToDevice));
     }
   }
   HIPC(hipMemcpy(ctx->d_probs, ctx->h_desc.data(), ctx->h_desc.size() * sizeof(DevProb), hipMemcpyHostToDevice));
+  return DSE_OK;
+}
+
+// Order of a lane's groups, which is the order of `items` and so of every launch: by tile size L;
+// within one L the real-component group first, then the spanning groups by descending
+// 16 span_L + span_rb, then the mixed group, then the problems of 1 tile, then of 2 (streaming:
+// ascending tiles per problem)
+struct GroupKey {
+  int L;
+  GroupKind kind;
+  int span_L, span_rb, tiles;  // span_*: kind Span, tiles: kind Tiles; else 0
+  bool operator<(const GroupKey& o) const {
+    auto rank = [](GroupKind k) { return k == GroupKind::Real ? 0 : k == GroupKind::Span ? 1 : k == GroupKind::Mixed ? 2 : 3; };
+    return std::make_tuple(L, rank(kind), -(16 * span_L + span_rb), tiles) <
+           std::make_tuple(o.L, rank(o.kind), -(16 * o.span_L + o.span_rb), o.tiles);
+  }
+};
+
+// per term k of the group's longest series: the items still active and the algorithmic bytes and
+// flops of the term's launch (pis in degree order)
+void fill_group_terms(const dse_ctx* ctx, LaneGroup& g, const std::vector<int>& pis) {
+  const int gdeg = ctx->probs[pis.front()].degree;
+  g.active.assign(gdeg + 2, 0);
+  g.bytes.assign(gdeg + 2, 0.0);
+  g.flops.assign(gdeg + 2, 0.0);
+  const double T = (double)(int64_t(1) << g.L);
+  for (int k = 0; k <= gdeg + 1; ++k) {
+    int64_t c = 0;
+    double by = 0.0, fl = 0.0;
+    for (int pi : pis) {
+      const int K = ctx->probs[pi].degree;
+      if (K < k) continue;
+      c += ctx->probs[pi].n_tiles;
+      fl += (double)ctx->probs[pi].n_tiles * T * ctx->probs[pi].flops_per_amp;
+      // read w_{k-1}, read+write w_{k-2}/w_k (48 B/amp), plus acc read+write on update terms
+      const bool upd = (k >= 2) && (((k - 1) % 3 == 0) || k == K);
+      by += (double)ctx->probs[pi].n_tiles * T * (upd ? 80.0 : 48.0);
+    }
+    g.active[k] = (int)c;
+    g.bytes[k] = by;
+    g.flops[k] = fl;
+  }
+}
+
+// ---- lanes ----
+// persistent: 2-tile problems on lane 0 (their workgroup pairs must be co-resident), 1-tile
+// problems on lane 1.  streaming: problems by degree dealt round-robin over the lanes.
+int assign_lanes(dse_ctx* ctx, EvolvePlan& pl) {
+  const bool persistent = pl.persistent;
   // dist shards: one lane, so the RCCL exchanges are stream-ordered with every launch
   int n_big = 0;
   for (auto& P : ctx->probs) n_big += P.side() ? 0 : 1;
-  const int n_lanes = any_dist ? 1 : std::max(1, std::min<int>(ctx->n_streams, n_big));
-  bool imag_all = true;
-  for (auto& P : ctx->probs) imag_all = imag_all && (P.side() || P.imag);
+  const int n_lanes = pl.n_lanes = pl.any_dist ? 1 : std::max(1, std::min<int>(ctx->n_streams, n_big));
+  for (auto& P : ctx->probs) pl.imag_all = pl.imag_all && (P.side() || P.imag);
   // 2-tile interval launches go out in chunks whose workgroups can all be resident at once (the
   // pairs hand off every term): the occupancy query x compute units, even.
-  int64_t pair_cap = 2;
   if (persistent) {
     int per_cu = 1;
     if (ctx->coresident > 0) {
-      pair_cap = ctx->coresident;
+      pl.cap = ctx->coresident;
     } else {
-      HIPC(interval_occupancy(13, imag_all, &per_cu));
-      pair_cap = (int64_t)std::max(1, per_cu) * ctx->n_cu;
+      HIPC(interval_occupancy(13, pl.imag_all, &per_cu));
+      pl.cap = (int64_t)std::max(1, per_cu) * ctx->n_cu;
     }
-    pair_cap = std::max<int64_t>(2, pair_cap / 2 * 2);
+    pl.cap = std::max<int64_t>(2, pl.cap / 2 * 2);
   }
-  const int64_t cap = pair_cap;
+  const int64_t cap = pl.cap;
   // Mixed launches (option mixed_launch): the 1- and 2-tile problems of one tile size share one
   // launch per interval instead of one stream each, so the 1-tile problems run in the CUs the
   // light 2-tile problems leave, inside the launch, and never hold a CU the next launch's stiff
@@ -3810,27 +3815,27 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
     return ctx->probs[a].degree > ctx->probs[b].degree;
   });
-  // lane -> (L, tiles per problem) -> problems
-  std::vector<std::map<std::pair<int, int64_t>, std::vector<int>>> lane_probs(n_lanes);
+  std::vector<std::map<GroupKey, std::vector<int>>> lane_probs(n_lanes);  // lane -> group -> problems
   for (size_t i = 0; i < order.size(); ++i) {
     const HostProblem& P = ctx->probs[order[i]];
     const bool mixed = mixed_L(P);
-    // tiles 0: a mixed group; < 0: spanning registers, -(16 L_span + rb)
     const int Ls = P.n_local - P.span_s;
-    const std::pair<int, int64_t> key(P.L, P.rl ? -1000 : P.span_s ? -(16 * Ls + span_rb_for(ctx, Ls))
-                                                                : (mixed ? 0 : P.n_tiles));
+    GroupKey key = {P.L, GroupKind::Tiles, 0, 0, 0};
+    if (P.rl) key.kind = GroupKind::Real;
+    else if (P.span_s) key.kind = GroupKind::Span, key.span_L = Ls, key.span_rb = span_rb_for(ctx, Ls);
+    else if (mixed) key.kind = GroupKind::Mixed;
+    else key.tiles = (int)P.n_tiles;
     int lane = (int)(i % n_lanes);
     if (persistent) lane = (P.n_tiles == 2 || n_lanes == 1 || mixed || P.span_s || P.rl) ? 0 : 1;
     // partial span: the spanned registers on a lane of their own, concurrent with k_interval's
-    if (persistent && P.span_s && !all_span && n_lanes >= 2) lane = n_lanes >= 3 ? 2 : 1;
+    if (persistent && P.span_s && !pl.all_span && n_lanes >= 2) lane = n_lanes >= 3 ? 2 : 1;
     // shards of one register read each other's vectors: same lane, hence the same launches
     if (P.shard_bits > 0 && !P.dist) lane = P.group_first % n_lanes;
     lane_probs[lane][key].push_back(order[i]);
   }
-  std::vector<int2> items;
+  std::vector<int2>& items = pl.items;
   items.reserve(ctx->total_items);
   ctx->item_pos.assign(ctx->probs.size(), 0);
-  int max_deg = 1;
   for (int li = 0; li < (int)ctx->lanes.size(); ++li) {
     Lane& ln = ctx->lanes[li];
     ln.groups.clear();
@@ -3838,11 +3843,11 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
     if (li >= n_lanes) continue;
     for (auto& kv : lane_probs[li]) {
       LaneGroup g;
-      g.L = kv.first.first;
-      g.tiles = (int)kv.first.second;
-      g.real = g.tiles == -1000;
-      if (g.real) g.tiles = 1;  // no hand-off flags, no pair placement
-      if (g.tiles < 0) g.span_L = (-g.tiles) / 16, g.span_rb = (-g.tiles) % 16;
+      g.L = kv.first.L;
+      g.kind = kv.first.kind;
+      g.tiles = kv.first.tiles;
+      g.span_L = kv.first.span_L;
+      g.span_rb = kv.first.span_rb;
       g.off = (int64_t)items.size();
       for (int pi : kv.second) {  // already in degree order
         ctx->item_pos[pi] = (int64_t)items.size();
@@ -3853,7 +3858,6 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
       g.wht_groups = persistent ? 0 : ctx->probs[kv.second.front()].wht_groups;
       for (int pi : kv.second)
         if (ctx->probs[pi].wht_groups != g.wht_groups) g.wht_groups = 0;
-      g.wht_regs.clear();
       if (g.wht_groups)
         for (int pi : kv.second) {
           const HostProblem& P = ctx->probs[pi];
@@ -3861,585 +3865,577 @@ static int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, doubl
           const int first = P.dist ? pi : P.group_first;
           if (P.dist || P.shard_rank == 0) g.wht_regs.push_back({first, P.degree});
         }
-      const int gdeg = ctx->probs[kv.second.front()].degree;
-      g.active.assign(gdeg + 2, 0);
-      g.bytes.assign(gdeg + 2, 0.0);
-      g.flops.assign(gdeg + 2, 0.0);
-      const double T = (double)(int64_t(1) << g.L);
-      for (int k = 0; k <= gdeg + 1; ++k) {
-        int64_t c = 0;
-        double by = 0.0, fl = 0.0;
-        for (int pi : kv.second) {
-          const int K = ctx->probs[pi].degree;
-          if (K < k) continue;
-          c += ctx->probs[pi].n_tiles;
-          fl += (double)ctx->probs[pi].n_tiles * T * ctx->probs[pi].flops_per_amp;
-          // read w_{k-1}, read+write w_{k-2}/w_k (48 B/amp), plus acc read+write on update terms
-          const bool upd = (k >= 2) && (((k - 1) % 3 == 0) || k == K);
-          by += (double)ctx->probs[pi].n_tiles * T * (upd ? 80.0 : 48.0);
-        }
-        g.active[k] = (int)c;
-        g.bytes[k] = by;
-        g.flops[k] = fl;
-      }
+      fill_group_terms(ctx, g, kv.second);
       ln.groups.push_back(std::move(g));
     }
-    max_deg = std::max(max_deg, ln.max_deg);
+    pl.max_deg = std::max(pl.max_deg, ln.max_deg);
   }
   HIPC(hipMemcpy(ctx->d_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice));
-  if (persistent) {
-    // Interval-kernel order of 2-tile groups: the two tiles of a problem exchange data every
-    // term, so place them 8 blocks apart -- blocks b and b + 8 land on one XCD under the
-    // observed round-robin dispatch and then hand off through that XCD's L2 (speed only; the
-    // hand-off protocol does not depend on placement).  Chunks of one launch are multiples of 16.
-    std::vector<int2> iv = items;
-    for (auto& ln : ctx->lanes)
-      for (auto& g : ln.groups) {
-        if (g.tiles == 0) {
-          // mixed group: the stiffest pairs first (as many as fit beside the 1-tile problems), then
-          // the 1-tile problems, then the remaining pairs, each segment in degree order; pairs in
-          // blocks of 16 with their tiles 8 apart, as below
-          std::vector<int2> pr, sg;
-          for (int64_t i = 0; i < g.count; ++i) {
-            const int2 e = items[g.off + i];
-            (ctx->probs[e.x].n_tiles == 2 ? pr : sg).push_back(e);
-          }
-          const int64_t np = (int64_t)pr.size() / 2, ns = (int64_t)sg.size();
-          const int64_t h = std::min<int64_t>(np, std::max<int64_t>(0, (cap - ns) / 2));
-          int64_t o = g.off;
-          auto put_pairs = [&](int64_t p0, int64_t p1) {
-            for (int64_t b0 = p0; b0 < p1; b0 += 8) {
-              const int64_t m = std::min<int64_t>(8, p1 - b0);
-              if (ctx->xcd_pairs) {
-                for (int64_t i = 0; i < m; ++i) {
-                  iv[o + i] = pr[2 * (b0 + i)];
-                  iv[o + m + i] = pr[2 * (b0 + i) + 1];
-                }
-              } else {
-                for (int64_t i = 0; i < 2 * m; ++i) iv[o + i] = pr[2 * b0 + i];
-              }
-              o += 2 * m;
-            }
-          };
-          put_pairs(0, h);
-          for (const int2& e : sg) iv[o++] = e;
-          put_pairs(h, np);
-          continue;
-        }
-        if (g.tiles != 2 || !ctx->xcd_pairs) continue;
-        for (int64_t off = 0; off < g.count; off += cap) {
-          const int64_t cnt = std::min<int64_t>(cap, g.count - off);
-          for (int64_t b0 = 0; b0 < cnt; b0 += 16) {
-            const int64_t m = std::min<int64_t>(16, cnt - b0) / 2;  // problems in this block
-            for (int64_t i = 0; i < m; ++i) {
-              iv[g.off + off + b0 + i] = items[g.off + off + b0 + 2 * i];
-              iv[g.off + off + b0 + m + i] = items[g.off + off + b0 + 2 * i + 1];
-            }
-          }
-        }
-      }
-    HIPC(hipMemcpy(ctx->d_items_iv, iv.data(), iv.size() * sizeof(int2), hipMemcpyHostToDevice));
-    // spanning groups: launch items (problem, tile); the tiles of one register 8 items apart, so
-    // under the round-robin dispatch of workgroups to the 8 XCDs they share one XCD's L2 (speed
-    // only), in blocks of 8 registers padded with items x = -1 (return at once)
-    std::vector<int2> sitems;
-    for (auto& ln : ctx->lanes)
-      for (auto& g : ln.groups) {
-        if (g.tiles >= 0) continue;
-        std::vector<int> pis;
-        for (int64_t i = 0; i < g.count; ++i) {
-          const int2 e = items[g.off + i];
-          if (pis.empty() || pis.back() != e.x) pis.push_back(e.x);
-        }
-        g.span_off = (int64_t)sitems.size();
-        int per_cu = 1;
-        HIPC(span_occupancy(g.span_L, g.span_rb, imag_all, &per_cu));
-        const int64_t resident = (int64_t)std::max(1, per_cu) * ctx->n_cu;
-        g.span_cuts.assign(1, 0);
-        g.span_am.assign(1, 0.0);
-        g.span_fl.assign(1, 0.0);
-        for (size_t b0 = 0; b0 < pis.size(); b0 += 8) {
-          int s = 0;  // the block's widest register sets its size (span_tile mixes 13 and 14 qubits)
-          for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i) s = std::max(s, ctx->probs[pis[i]].span_s);
-          const size_t base = sitems.size();
-          if ((int64_t)(base + ((size_t)8 << s)) - g.span_off - g.span_cuts.back() > resident &&
-              (int64_t)base - g.span_off > g.span_cuts.back()) {
-            g.span_cuts.push_back((int64_t)base - g.span_off);  // this block starts the next launch
-            g.span_am.push_back(0.0);
-            g.span_fl.push_back(0.0);
-          }
-          for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i) {
-            const HostProblem& P = ctx->probs[pis[i]];
-            g.span_am.back() += std::ldexp(1.0, P.n_local) * P.degree;
-            g.span_fl.back() += std::ldexp(1.0, P.n_local) * P.degree * P.flops_per_amp;
-          }
-          sitems.resize(base + ((size_t)8 << s), make_int2(-1, 0));
-          for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i)
-            for (int h = 0; h < (1 << ctx->probs[pis[i]].span_s); ++h)
-              sitems[base + (size_t)h * 8 + (i - b0)] = make_int2(pis[i], h);
-        }
-        g.span_count = (int64_t)sitems.size() - g.span_off;
-        g.span_cuts.push_back(g.span_count);
-      }
-    // real-component groups: items (problem, component) in degree order, then (problem, 0) per
-    // problem for the combine launch
-    std::vector<int2> ritems;
-    for (auto& ln : ctx->lanes)
-      for (auto& g : ln.groups) {
-        if (!g.real) continue;
-        std::vector<int> pis;
-        for (int64_t i = 0; i < g.count; ++i) {
-          const int2 e = items[g.off + i];
-          if (pis.empty() || pis.back() != e.x) pis.push_back(e.x);
-        }
-        g.real_off = (int64_t)ritems.size();
-        for (int pi : pis) ritems.push_back(make_int2(pi, 0)), ritems.push_back(make_int2(pi, 1));
-        g.real_count = (int64_t)ritems.size() - g.real_off;
-        g.real_poff = (int64_t)ritems.size();
-        for (int pi : pis) ritems.push_back(make_int2(pi, 0));
-        g.real_np = (int64_t)pis.size();
-      }
-    if (!ritems.empty()) {
-      if (ritems.size() > ctx->real_items_cap) {
-        if (ctx->d_real_items) (void)hipFree(ctx->d_real_items), ctx->d_real_items = nullptr;
-        ctx->real_items_cap = 0;
-        if (hipMalloc(&ctx->d_real_items, ritems.size() * sizeof(int2)) != hipSuccess)
-          return fail(ctx, DSE_ERR_OOM, "real item allocation failed");
-        ctx->real_items_cap = ritems.size();
-      }
-      HIPC(hipMemcpy(ctx->d_real_items, ritems.data(), ritems.size() * sizeof(int2), hipMemcpyHostToDevice));
-    }
-    if (!sitems.empty()) {
-      if (sitems.size() > ctx->span_items_cap) {
-        if (ctx->d_span_items) (void)hipFree(ctx->d_span_items), ctx->d_span_items = nullptr;
-        ctx->span_items_cap = 0;
-        if (hipMalloc(&ctx->d_span_items, sitems.size() * sizeof(int2)) != hipSuccess)
-          return fail(ctx, DSE_ERR_OOM, "span item allocation failed");
-        ctx->span_items_cap = sitems.size();
-      }
-      HIPC(hipMemcpy(ctx->d_span_items, sitems.data(), sitems.size() * sizeof(int2), hipMemcpyHostToDevice));
-    }
-  }
-  if (persistent) {
-    const size_t need = 2 * kIvWaves * ctx->probs.size() + 1;  // flags, error word
-    if (ctx->flags_cap < need) {
-      if (ctx->d_flags) (void)hipFree(ctx->d_flags), ctx->d_flags = nullptr;
-      if (hipMalloc(&ctx->d_flags, need * sizeof(int)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "flag allocation failed");
-      ctx->flags_cap = need;
-    }
-    HIPC(hipMemset(ctx->d_flags, 0, need * sizeof(int)));
-  }
-  int* d_err = persistent ? ctx->d_flags + 2 * kIvWaves * ctx->probs.size() : nullptr;
-  ctx->d_err_cur = d_err;  // checked by every flush_partials (reset by dse_evolve on return)
+  return DSE_OK;
+}
 
-  phase("lanes/items");
-  // ---- psi(t0) = |psi0> ----
-  hipStream_t st0 = ctx->lanes[0].stream;
-  {
-    std::vector<BasisInit> init;
-    std::vector<HostProblem*> custom;  // registers (shards) that start from a stored or product state
-    uint64_t max_amps = 0;
-    for (auto& P : ctx->probs) {
-      // the re-run after a hand-off timeout keeps the dense registers' first-pass results, whose
-      // final state k_dense_final wrote into buf[0]
-      if (ctx->rerun && P.dn) continue;
-      if (P.init_kind) {
-        custom.push_back(&P);
+// Interval-kernel order of 2-tile groups: the two tiles of a problem exchange data every
+// term, so place them 8 blocks apart -- blocks b and b + 8 land on one XCD under the
+// observed round-robin dispatch and then hand off through that XCD's L2 (speed only; the
+// hand-off protocol does not depend on placement).  Chunks of one launch are multiples of 16.
+int order_interval_items(dse_ctx* ctx, const EvolvePlan& pl) {
+  const std::vector<int2>& items = pl.items;
+  const int64_t cap = pl.cap;
+  std::vector<int2> iv = items;
+  for (auto& ln : ctx->lanes)
+    for (auto& g : ln.groups) {
+      if (g.kind == GroupKind::Mixed) {
+        // mixed group: the stiffest pairs first (as many as fit beside the 1-tile problems), then
+        // the 1-tile problems, then the remaining pairs, each segment in degree order; pairs in
+        // blocks of 16 with their tiles 8 apart, as below
+        std::vector<int2> pr, sg;
+        for (int64_t i = 0; i < g.count; ++i) {
+          const int2 e = items[g.off + i];
+          (ctx->probs[e.x].n_tiles == 2 ? pr : sg).push_back(e);
+        }
+        const int64_t np = (int64_t)pr.size() / 2, ns = (int64_t)sg.size();
+        const int64_t h = std::min<int64_t>(np, std::max<int64_t>(0, (cap - ns) / 2));
+        int64_t o = g.off;
+        auto put_pairs = [&](int64_t p0, int64_t p1) {
+          for (int64_t b0 = p0; b0 < p1; b0 += 8) {
+            const int64_t m = std::min<int64_t>(8, p1 - b0);
+            if (ctx->xcd_pairs) {
+              for (int64_t i = 0; i < m; ++i) {
+                iv[o + i] = pr[2 * (b0 + i)];
+                iv[o + m + i] = pr[2 * (b0 + i) + 1];
+              }
+            } else {
+              for (int64_t i = 0; i < 2 * m; ++i) iv[o + i] = pr[2 * b0 + i];
+            }
+            o += 2 * m;
+          }
+        };
+        put_pairs(0, h);
+        for (const int2& e : sg) iv[o++] = e;
+        put_pairs(h, np);
         continue;
       }
-      BasisInit e;
-      e.ptr = P.buf[0];
-      e.n = uint64_t(1) << P.n_local;
-      // the shard holding psi0 (every unsharded register)
-      e.one_at = ((P.psi0 >> P.n_local) == (uint64_t)P.shard_rank)
-                     ? (int64_t)(P.psi0 & ((uint64_t(1) << P.n_local) - 1)) : -1;
-      init.push_back(e);
-      max_amps = std::max(max_amps, e.n);
-    }
-    if (init.size() > ctx->init_cap) {
-      if (ctx->d_init) (void)hipFree(ctx->d_init), ctx->d_init = nullptr;
-      ctx->init_cap = 0;
-      if (hipMalloc(&ctx->d_init, init.size() * sizeof(BasisInit)) != hipSuccess)
-        return fail(ctx, DSE_ERR_OOM, "initial-state list allocation failed");
-      ctx->init_cap = init.size();
-    }
-    if (ctx->dbg & 2) {
-      for (auto& e : init) {
-        HIPC(hipMemsetAsync(e.ptr, 0, e.n * sizeof(double2), st0));
-        static const double2 one = {1.0, 0.0};
-        if (e.one_at >= 0) HIPC(hipMemcpyAsync(e.ptr + e.one_at, &one, sizeof(double2), hipMemcpyHostToDevice, st0));
-      }
-    } else {
-      HIPC(hipMemcpyAsync(ctx->d_init, init.data(), init.size() * sizeof(BasisInit), hipMemcpyHostToDevice, st0));
-      for (size_t i0 = 0; i0 < init.size(); i0 += 65535)
-        HIPC(launch_basis_init(ctx->d_init + i0, (int)std::min<size_t>(65535, init.size() - i0), max_amps, st0));
-    }
-    // custom psi(t0) (the re-run after a hand-off timeout comes through here again: the same state)
-    for (HostProblem* P : custom) {
-      if (P->init_kind == 1)
-        HIPC(hipMemcpyAsync(P->buf[0], P->init_state, (size_t(1) << P->n_local) * sizeof(double2),
-                            hipMemcpyDeviceToDevice, st0));
-      else
-        HIPC(launch_product_state(P->buf[0], P->d_init_amp, P->n, P->n_local, (uint64_t)P->shard_rank, st0));
-    }
-    for (auto& ln : ctx->lanes)  // real-component registers: [a | b] = [e_x0 | 0], or split from buf[0]
-      for (auto& g : ln.groups)
-        if (g.real) {
-          HIPC(launch_real_init(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, st0));
-          if (!custom.empty())
-            HIPC(launch_real_split(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, st0));
+      if (g.kind != GroupKind::Tiles || g.tiles != 2 || !ctx->xcd_pairs) continue;
+      for (int64_t off = 0; off < g.count; off += cap) {
+        const int64_t cnt = std::min<int64_t>(cap, g.count - off);
+        for (int64_t b0 = 0; b0 < cnt; b0 += 16) {
+          const int64_t m = std::min<int64_t>(16, cnt - b0) / 2;  // problems in this block
+          for (int64_t i = 0; i < m; ++i) {
+            iv[g.off + off + b0 + i] = items[g.off + off + b0 + 2 * i];
+            iv[g.off + off + b0 + m + i] = items[g.off + off + b0 + 2 * i + 1];
+          }
         }
-    HIPC(hipStreamSynchronize(st0));
-  }
-  double small_happl = 0.0, small_launches = 0.0;
-  if (any_small && (rc = small_launch(ctx, t, n_t, tol, &small_happl, &small_launches))) return rc;
+      }
+    }
+  HIPC(hipMemcpy(ctx->d_items_iv, iv.data(), iv.size() * sizeof(int2), hipMemcpyHostToDevice));
+  return DSE_OK;
+}
 
-  double dense_ms = 0.0, dense_eig_ms = 0.0;
+// the problems of a group, in item order
+std::vector<int> group_problems(const EvolvePlan& pl, const LaneGroup& g) {
+  std::vector<int> pis;
+  for (int64_t i = 0; i < g.count; ++i) {
+    const int2 e = pl.items[g.off + i];
+    if (pis.empty() || pis.back() != e.x) pis.push_back(e.x);
+  }
+  return pis;
+}
+
+// spanning groups: launch items (problem, tile); the tiles of one register 8 items apart, so
+// under the round-robin dispatch of workgroups to the 8 XCDs they share one XCD's L2 (speed
+// only), in blocks of 8 registers padded with items x = -1 (return at once)
+int order_span_items(dse_ctx* ctx, EvolvePlan& pl) {
+  std::vector<int2>& sitems = pl.span_items;
+  for (auto& ln : ctx->lanes)
+    for (auto& g : ln.groups) {
+      if (g.kind != GroupKind::Span) continue;
+      const std::vector<int> pis = group_problems(pl, g);
+      g.span_off = (int64_t)sitems.size();
+      int per_cu = 1;
+      HIPC(span_occupancy(g.span_L, g.span_rb, pl.imag_all, &per_cu));
+      const int64_t resident = (int64_t)std::max(1, per_cu) * ctx->n_cu;
+      g.span_cuts.assign(1, 0);
+      g.span_am.assign(1, 0.0);
+      g.span_fl.assign(1, 0.0);
+      for (size_t b0 = 0; b0 < pis.size(); b0 += 8) {
+        int s = 0;  // the block's widest register sets its size (span_tile mixes 13 and 14 qubits)
+        for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i) s = std::max(s, ctx->probs[pis[i]].span_s);
+        const size_t base = sitems.size();
+        if ((int64_t)(base + ((size_t)8 << s)) - g.span_off - g.span_cuts.back() > resident &&
+            (int64_t)base - g.span_off > g.span_cuts.back()) {
+          g.span_cuts.push_back((int64_t)base - g.span_off);  // this block starts the next launch
+          g.span_am.push_back(0.0);
+          g.span_fl.push_back(0.0);
+        }
+        for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i) {
+          const HostProblem& P = ctx->probs[pis[i]];
+          g.span_am.back() += std::ldexp(1.0, P.n_local) * P.degree;
+          g.span_fl.back() += std::ldexp(1.0, P.n_local) * P.degree * P.flops_per_amp;
+        }
+        sitems.resize(base + ((size_t)8 << s), make_int2(-1, 0));
+        for (size_t i = b0; i < std::min(pis.size(), b0 + 8); ++i)
+          for (int h = 0; h < (1 << ctx->probs[pis[i]].span_s); ++h)
+            sitems[base + (size_t)h * 8 + (i - b0)] = make_int2(pis[i], h);
+      }
+      g.span_count = (int64_t)sitems.size() - g.span_off;
+      g.span_cuts.push_back(g.span_count);
+    }
+  return DSE_OK;
+}
+
+// real-component groups: items (problem, component) in degree order, then (problem, 0) per
+// problem for the combine launch
+void order_real_items(dse_ctx* ctx, EvolvePlan& pl) {
+  std::vector<int2>& ritems = pl.real_items;
+  for (auto& ln : ctx->lanes)
+    for (auto& g : ln.groups) {
+      if (g.kind != GroupKind::Real) continue;
+      const std::vector<int> pis = group_problems(pl, g);
+      g.real_off = (int64_t)ritems.size();
+      for (int pi : pis) ritems.push_back(make_int2(pi, 0)), ritems.push_back(make_int2(pi, 1));
+      g.real_count = (int64_t)ritems.size() - g.real_off;
+      g.real_poff = (int64_t)ritems.size();
+      for (int pi : pis) ritems.push_back(make_int2(pi, 0));
+      g.real_np = (int64_t)pis.size();
+    }
+}
+
+// the real and span items (persistent only) to the device; the hand-off flags and the error word, zeroed
+int upload_items_and_flags(dse_ctx* ctx, EvolvePlan& pl) {
+  int rc;
+  if (!pl.real_items.empty()) {
+    if ((rc = ctx->d_real_items.reserve(ctx, pl.real_items.size(), "real item allocation failed"))) return rc;
+    HIPC(hipMemcpy(ctx->d_real_items.p, pl.real_items.data(), pl.real_items.size() * sizeof(int2), hipMemcpyHostToDevice));
+  }
+  if (!pl.span_items.empty()) {
+    if ((rc = ctx->d_span_items.reserve(ctx, pl.span_items.size(), "span item allocation failed"))) return rc;
+    HIPC(hipMemcpy(ctx->d_span_items.p, pl.span_items.data(), pl.span_items.size() * sizeof(int2), hipMemcpyHostToDevice));
+  }
+  if (pl.persistent) {
+    const size_t need = 2 * kIvWaves * ctx->probs.size() + 1;  // flags, error word
+    if ((rc = ctx->d_flags.reserve(ctx, need, "flag allocation failed"))) return rc;
+    HIPC(hipMemset(ctx->d_flags.p, 0, need * sizeof(int)));
+    pl.d_err = ctx->d_flags.p + 2 * kIvWaves * ctx->probs.size();
+  }
+  ctx->d_err_cur = pl.d_err;  // checked by every flush_partials (reset by dse_evolve on return)
+  return DSE_OK;
+}
+
+// ---- psi(t0) = |psi0>, or the register's stored or product state ----
+int write_initial_states(dse_ctx* ctx, const EvolvePlan& pl) {
+  hipStream_t st0 = ctx->lanes[0].stream;
+  std::vector<BasisInit> init;
+  std::vector<HostProblem*> custom;  // registers (shards) that start from a stored or product state
+  uint64_t max_amps = 0;
+  for (auto& P : ctx->probs) {
+    // the re-run after a hand-off timeout keeps the dense registers' first-pass results, whose
+    // final state k_dense_final wrote into buf[0]
+    if (ctx->rerun && P.dn) continue;
+    if (P.init_kind) {
+      custom.push_back(&P);
+      continue;
+    }
+    BasisInit e;
+    e.ptr = P.buf[0];
+    e.n = uint64_t(1) << P.n_local;
+    // the shard holding psi0 (every unsharded register)
+    e.one_at = ((P.psi0 >> P.n_local) == (uint64_t)P.shard_rank)
+                   ? (int64_t)(P.psi0 & ((uint64_t(1) << P.n_local) - 1)) : -1;
+    init.push_back(e);
+    max_amps = std::max(max_amps, e.n);
+  }
+  if (int rc = ctx->d_init.reserve(ctx, init.size(), "initial-state list allocation failed")) return rc;
+  if (ctx->dbg & 2) {
+    for (auto& e : init) {
+      HIPC(hipMemsetAsync(e.ptr, 0, e.n * sizeof(double2), st0));
+      static const double2 one = {1.0, 0.0};
+      if (e.one_at >= 0) HIPC(hipMemcpyAsync(e.ptr + e.one_at, &one, sizeof(double2), hipMemcpyHostToDevice, st0));
+    }
+  } else {
+    HIPC(hipMemcpyAsync(ctx->d_init.p, init.data(), init.size() * sizeof(BasisInit), hipMemcpyHostToDevice, st0));
+    for (size_t i0 = 0; i0 < init.size(); i0 += 65535)
+      HIPC(launch_basis_init(ctx->d_init.p + i0, (int)std::min<size_t>(65535, init.size() - i0), max_amps, st0));
+  }
+  // custom psi(t0) (the re-run after a hand-off timeout comes through here again: the same state)
+  for (HostProblem* P : custom) {
+    if (P->init_kind == 1)
+      HIPC(hipMemcpyAsync(P->buf[0], P->init_state, (size_t(1) << P->n_local) * sizeof(double2),
+                          hipMemcpyDeviceToDevice, st0));
+    else
+      HIPC(launch_product_state(P->buf[0], P->d_init_amp, P->n, P->n_local, (uint64_t)P->shard_rank, st0));
+  }
+  for (auto& ln : ctx->lanes)  // real-component registers: [a | b] = [e_x0 | 0], or split from buf[0]
+    for (auto& g : ln.groups)
+      if (g.kind == GroupKind::Real) {
+        HIPC(launch_real_init(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, st0));
+        if (!custom.empty())
+          HIPC(launch_real_split(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, st0));
+      }
+  HIPC(hipStreamSynchronize(st0));
+  return DSE_OK;
+}
+
+// the engines beside the per-interval launches: small registers, dense registers, matrix mode
+int run_side_engines(dse_ctx* ctx, EvolvePlan& pl) {
+  int rc;
+  if (pl.any_small && (rc = small_launch(ctx, pl.t, pl.n_t, pl.tol, &pl.small_happl, &pl.small_launches))) return rc;
   // (the re-run after a hand-off timeout keeps the first pass's dense results: dense_run completed
   // and wrote them before any interval launch, and its register choice depends only on t)
-  if (any_dense && !ctx->rerun && (rc = dense_run(ctx, t, n_t, obs_out, &dense_ms, &dense_eig_ms))) return rc;
-  double matrix_happl = 0.0;
-  if (matrix_pi >= 0 && (rc = matrix_run(ctx, matrix_pi, t, n_t, matrix_dt, tol, obs_out, &matrix_happl))) return rc;
-  phase("psi0/small");
-  size_t chunk = (size_t)std::max<int64_t>(M, std::min<int64_t>(
-      n_t, std::max<int64_t>(1, (int64_t)(256ll << 20) / (ctx->total_items * 64))));
-  if (ctx->site_obs) {  // slots per flush: what both arenas hold under the same 256 MiB cap
-    int n_max = 1;
-    for (const auto& P : ctx->probs) n_max = std::max(n_max, P.n);
-    const int64_t per_slot = ctx->total_items * (int64_t)site_stride(n_max) * 8;
-    chunk = std::min(chunk, (size_t)std::max<int64_t>(M, std::min<int64_t>(
-                                n_t, std::max<int64_t>(1, (int64_t)(256ll << 20) / per_slot))));
-  }
-  if (ctx->pair_obs) {  // the third arena likewise (one slot fits the cap: pair_refusal)
-    const int64_t per_slot = std::max<int64_t>(1, ctx->total_items) * (int64_t)pair_stride(pair_n_max(ctx)) * 8;
-    chunk = std::min(chunk, (size_t)std::max<int64_t>(M, std::min<int64_t>(
-                                n_t, std::max<int64_t>(1, kPartialCapBytes / per_slot))));
-  }
-  if (ctx->site_obs && (rc = ensure_site_partial(ctx, chunk))) return rc;
-  if (ctx->pair_obs && (rc = ensure_pair_partial(ctx, chunk))) return rc;
-  const bool sites_on = ctx->site_obs != 0, pairs_on = ctx->pair_obs != 0;
-  if ((rc = ensure_partial(ctx, chunk))) return rc;
+  if (pl.any_dense && !ctx->rerun && (rc = dense_run(ctx, pl.t, pl.n_t, pl.obs_out, &pl.dense_ms, &pl.dense_eig_ms)))
+    return rc;
+  if (pl.matrix_pi >= 0 &&
+      (rc = matrix_run(ctx, pl.matrix_pi, pl.t, pl.n_t, pl.matrix_dt, pl.tol, pl.obs_out, &pl.matrix_happl)))
+    return rc;
+  return DSE_OK;
+}
+
+// output slots per flush: what every arena in use holds under kPartialCapBytes (for the pair
+// arena one slot fits the cap: pair_refusal); the arenas; the timing events
+int size_obs_chunks(dse_ctx* ctx, EvolvePlan& pl) {
+  const int64_t tiles = ctx->total_items;
+  const int n_max = widest_register(ctx);
+  int rc;
+  pl.chunk = partial_chunk(tiles * 64, pl.M, pl.n_t);
+  if (ctx->site_obs) pl.chunk = std::min(pl.chunk, partial_chunk(tiles * site_stride(n_max) * 8, pl.M, pl.n_t));
+  if (ctx->pair_obs)
+    pl.chunk = std::min(pl.chunk, partial_chunk(std::max<int64_t>(1, tiles) * pair_stride(n_max) * 8, pl.M, pl.n_t));
+  if (ctx->site_obs && (rc = ensure_site_partial(ctx, pl.chunk))) return rc;
+  if (ctx->pair_obs && (rc = ensure_pair_partial(ctx, pl.chunk))) return rc;
+  if ((rc = ensure_partial(ctx, pl.chunk))) return rc;
   if (ctx->time_every > 0)
     for (auto& ln : ctx->lanes) {
       // timed launches per interval and pool: one per term and group (streaming), one per
       // co-resident chunk and group (persistent); records beyond the pool are skipped, not timed
       size_t need = 1;
       for (const auto& g : ln.groups)
-        need += persistent ? (g.tiles < 0 ? g.span_cuts.size() - 1 : (size_t)((g.count + cap - 1) / cap))
-                           : (size_t)(ln.max_deg + 1);
+        need += pl.persistent ? (g.kind == GroupKind::Span ? g.span_cuts.size() - 1 : (size_t)((g.count + pl.cap - 1) / pl.cap))
+                              : (size_t)(ln.max_deg + 1);
       if ((rc = ensure_events(ctx, ln, need))) return rc;
     }
+  return DSE_OK;
+}
 
-  double step_ms = 0.0, launches_timed = 0.0, bytes_timed = 0.0, amps_timed = 0.0;
-  double lane0_ms = 0.0, lane0_launches = 0.0, lane0_amps = 0.0;  // lane 0 alone (stats)
-  double launches = 0.0, amp_updates = 0.0, all_bytes = 0.0, all_flops = 0.0, flops_timed = 0.0;
-  // per timed launch: algorithmic flops (pool_bytes), HBM bytes (pool_bytes2, streaming only) and
-  // amplitude-terms (pool_amps: amplitudes x Chebyshev terms the launch computes)
-  std::vector<std::vector<double>> pool_bytes(ctx->lanes.size() * 2), pool_bytes2(ctx->lanes.size() * 2),
-      pool_amps(ctx->lanes.size() * 2);
-  auto drain = [&](Lane& ln, size_t li, int pool) -> int {
-    if (ln.ev_used[pool] == 0) return DSE_OK;
-    HIPC(hipEventSynchronize(ln.ev[pool][2 * ln.ev_used[pool] - 1]));
-    for (size_t i = 0; i < ln.ev_used[pool]; ++i) {
-      float ms = 0.f;
-      HIPC(hipEventElapsedTime(&ms, ln.ev[pool][2 * i], ln.ev[pool][2 * i + 1]));
-      step_ms += ms;
-      flops_timed += pool_bytes[li * 2 + pool][i];
-      amps_timed += pool_amps[li * 2 + pool][i];
-      if (li == 0) lane0_ms += ms, lane0_amps += pool_amps[li * 2 + pool][i], lane0_launches += 1.0;
-      if (i < pool_bytes2[li * 2 + pool].size()) bytes_timed += pool_bytes2[li * 2 + pool][i];
-    }
-    launches_timed += (double)ln.ev_used[pool];
-    ln.ev_used[pool] = 0;
-    pool_bytes[li * 2 + pool].clear();
-    pool_bytes2[li * 2 + pool].clear();
-    pool_amps[li * 2 + pool].clear();
-    return DSE_OK;
-  };
-  // observables of n_out consecutive output slots (one launch per lane group): outputs
-  // j < n_out - 1 from the intermediate accumulators, the last from state role bsel_q
-  // obs_ovl: on each lane's obs_stream behind the lane's interval launches of parity xq (event
-  // ev_iv[xq]), then ev_obs[xq] for the launches two groups later, which rewrite these buffers
-  auto obs_all = [&](int bsel_q, size_t slot, int n_out, int xq) -> int {
-    for (auto& ln : ctx->lanes) {
-      if (ln.groups.empty()) continue;
-      hipStream_t os = obs_ovl ? ln.obs_stream : ln.stream;
-      if (obs_ovl) {
-        HIPC(hipEventRecord(ln.ev_iv[xq], ln.stream));
-        HIPC(hipStreamWaitEvent(os, ln.ev_iv[xq], 0));
-      }
-      for (auto& g : ln.groups) {
-        HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
-                        ctx->d_partial + (slot * ctx->total_items + g.off) * 8, os, n_out,
-                        (size_t)ctx->total_items * 8, xq));
-        if (sites_on)
-          HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
-                                ctx->d_site_partial + (slot * ctx->total_items + g.off) * ctx->site_S,
-                                ctx->site_S, os, n_out, (size_t)ctx->total_items * ctx->site_S, xq));
-        if (pairs_on)
-          HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel_q,
-                                ctx->d_pair_partial + (slot * ctx->total_items + g.off) * ctx->pair_S,
-                                ctx->pair_S, os, n_out, (size_t)ctx->total_items * ctx->pair_S, xq));
-      }
-      if (obs_ovl) {
-        HIPC(hipEventRecord(ln.ev_obs[xq], os));
-        ln.obs_pending[xq] = true;
-      }
-    }
-    return DSE_OK;
-  };
-  for (auto& ln : ctx->lanes) ln.obs_pending[0] = ln.obs_pending[1] = false;
+// The aggregate, site and pair observables of one lane group: state role bsel of its problems into
+// arena slot `slot`; with n_out > 1 outputs j < n_out - 1 from the intermediate accumulators of
+// parity xq into the slots before it (out_stride_slots = 1)
+int launch_group_obs(dse_ctx* ctx, const LaneGroup& g, int bsel, size_t slot, int n_out,
+                            size_t out_stride_slots, int xq, hipStream_t st) {
+  const size_t at = slot * ctx->total_items + g.off, stride = out_stride_slots * (size_t)ctx->total_items;
+  HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel, ctx->d_partial.p + at * 8, st, n_out,
+                  stride * 8, xq));
+  if (ctx->site_obs)
+    HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel,
+                          ctx->d_site_partial.p + at * ctx->site_S, ctx->site_S, st, n_out, stride * ctx->site_S, xq));
+  if (ctx->pair_obs)
+    HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel,
+                          ctx->d_pair_partial.p + at * ctx->pair_S, ctx->pair_S, st, n_out, stride * ctx->pair_S, xq));
+  return DSE_OK;
+}
 
-  std::vector<double> dist_raw(any_dist ? ctx->probs.size() * (size_t)n_t * 7 : 0, 0.0);
-  size_t slot = 0, t_flushed = 0;
-  if (any_dist && (rc = dist_exchange(ctx, 0, 0, ctx->lanes[0].stream))) return rc;
-  if ((rc = obs_all(0, slot++, 1, 1))) return rc;
-  for (int gi = 0; gi < n_groups; ++gi) {
-    const Group& G = groups[gi];
-    const int q = gi & 1;
-    const int set = G.set;
-    const bool timed = ctx->time_every > 0 && (gi % ctx->time_every) == 0;
-    const int pool = gi & 1;
-    for (size_t li = 0; li < ctx->lanes.size(); ++li) {
-      Lane& ln = ctx->lanes[li];
-      if (ln.groups.empty()) continue;
-      if ((rc = drain(ln, li, pool))) return rc;
-      if (obs_ovl && ln.obs_pending[q]) {  // the observables that read what this group rewrites
-        HIPC(hipStreamWaitEvent(ln.stream, ln.ev_obs[q], 0));
-        ln.obs_pending[q] = false;
-      }
-      for (auto& g : ln.groups) {
-        const int T = 1 << g.L;
-        if (persistent) {
-          // all K terms of the interval in one launch; 2-tile groups in co-resident chunks;
-          // spanning registers: one k_span launch per chunk of span_cuts (each chunk's registers'
-          // tiles all resident at once: the cuts are sized to the chip's resident capacity), flags
-          // zeroed first
-          if (g.tiles < 0) HIPC(hipMemsetAsync(ctx->d_span_flags, 0, ctx->span_flag_cap, ln.stream));
-          else if (g.tiles != 1) HIPC(zero_flags(ctx->d_items + g.off, (int)g.count, ctx->d_flags, ln.stream));
-          auto launch_g = [&](int64_t off, int cnt) -> hipError_t {
-            if (g.real)
-              return launch_real(ctx->d_probs, ctx->d_real_items + g.real_off, (int)g.real_count, set, G.n_out,
-                                 ln.stream);
-            if (g.tiles < 0)  // chunk [off, off + cnt) of the group's span launches
-              return launch_span(g.span_L, g.span_rb, imag_all, ctx->d_probs, ctx->d_span,
-                                 ctx->d_span_items + g.span_off + g.span_cuts[off],
-                                 (int)(g.span_cuts[off + cnt] - g.span_cuts[off]), q, set, G.n_out, d_err, ctx->hk,
-                                 ln.stream);
-            return launch_interval(g.L, imag_all, ctx->d_probs, ctx->d_items_iv + g.off + off, cnt, q, set, G.n_out,
-                                   ctx->d_flags, d_err, ctx->hk, ln.stream);
-          };
-          // mixed (0): one launch; 2-tile: co-resident chunks of cap items; span (< 0): one launch
-          // per chunk of span_cuts (off / cnt then count chunks, not items)
-          const int64_t gcap = g.tiles == 2 ? cap : g.tiles < 0 ? 1 : g.count;
-          const int64_t gn = g.tiles < 0 ? (int64_t)g.span_cuts.size() - 1 : g.count;
-          for (int64_t off = 0; off < gn; off += gcap) {
-            const int cnt = (int)std::min<int64_t>(gcap, gn - off);
-            double fl = 0.0, am = 0.0;
-            if (g.tiles < 0) {  // the chunk's registers
-              am = g.span_am[off];
-              fl = g.span_fl[off];
-            } else {
-              for (int64_t i = off; i < off + cnt; ++i) {
-                const HostProblem& P = ctx->probs[items[g.off + i].x];
-                am += (double)T * P.degree;
-                fl += (double)T * P.degree * P.flops_per_amp;
-              }
-            }
-            if (timed && 2 * ln.ev_used[pool] + 2 <= ln.ev[pool].size()) {
-              const size_t i = ln.ev_used[pool]++;
-              HIPC(hipEventRecord(ln.ev[pool][2 * i], ln.stream));
-              HIPC(launch_g(off, cnt));
-              HIPC(hipEventRecord(ln.ev[pool][2 * i + 1], ln.stream));
-              pool_bytes[li * 2 + pool].push_back(fl);
-              pool_amps[li * 2 + pool].push_back(am);
-            } else {
-              HIPC(launch_g(off, cnt));
-            }
-            launches += 1.0;
-            amp_updates += am;
-            all_flops += fl;
-          }
-          // real-component registers: psi of every output (computational frame) and the next [a | b]
-          if (g.real)
-            HIPC(launch_real_combine(ctx->d_probs, ctx->d_real_items + g.real_poff, (int)g.real_np, q, G.n_out,
-                                     ln.stream));
-          continue;
-        }
-        if (any_dist_step && (rc = dist_exchange(ctx, q ? 2 : 0, 1, ln.stream))) return rc;
-        // fused FINAL + FIRST for the whole evolve, or not at all: a group with any partitioned
-        // register (index swaps around MID) runs unfused, also on the terms past that register's degree
-        const bool fuse = ctx->wht_fuse && g.wht_regs.empty();
-        auto step = [&](int mode, int na, int k) -> int {
-          if (g.wht_groups) {
-            std::vector<int> regs;
-            for (const auto& rg : g.wht_regs)
-              if (rg.second >= k) regs.push_back(rg.first);
-            return wht_run(ctx, g.L, g.wht_groups, {{ctx->d_items + g.off, na}}, regs, fuse, mode, k, q, set,
-                           ln.stream);
-          }
-          HIPC(launch_step(g.L, mode, ctx->d_probs, ctx->d_items + g.off, na, k, q, set, ln.stream));
-          return DSE_OK;
-        };
-        if ((rc = step(MODE_FIRST, g.active[1], 1))) return rc;
-        for (int k = 2; k < (int)g.active.size(); ++k) {
-          const int na = g.active[k];
-          if (na <= 0) break;
-          if (any_dist_step && (rc = dist_exchange(ctx, ((k - 1) & 1) ? 1 : (q ? 2 : 0), k, ln.stream)))
-            return rc;
-          if (timed && 2 * ln.ev_used[pool] + 2 <= ln.ev[pool].size()) {
-            const size_t i = ln.ev_used[pool]++;
-            HIPC(hipEventRecord(ln.ev[pool][2 * i], ln.stream));
-            if ((rc = step(MODE_GEN, na, k))) return rc;
-            HIPC(hipEventRecord(ln.ev[pool][2 * i + 1], ln.stream));
-            pool_bytes[li * 2 + pool].push_back(g.flops[k]);
-            pool_bytes2[li * 2 + pool].push_back(g.bytes[k]);
-            pool_amps[li * 2 + pool].push_back((double)na * T);
-          } else {
-            if ((rc = step(MODE_GEN, na, k))) return rc;
-          }
-          launches += 1.0;
-          amp_updates += (double)na * T;
-          all_bytes += g.bytes[k];
-          all_flops += g.flops[k];
-        }
-      }
+// observables of n_out consecutive output slots (one launch per lane group): outputs
+// j < n_out - 1 from the intermediate accumulators, the last from state role bsel_q
+// obs_ovl: on each lane's obs_stream behind the lane's interval launches of parity xq (event
+// ev_iv[xq]), then ev_obs[xq] for the launches two groups later, which rewrite these buffers
+int launch_all_obs(dse_ctx* ctx, const EvolvePlan& pl, int bsel_q, size_t slot, int n_out, int xq) {
+  for (auto& ln : ctx->lanes) {
+    if (ln.groups.empty()) continue;
+    hipStream_t os = pl.obs_ovl ? ln.obs_stream : ln.stream;
+    if (pl.obs_ovl) {
+      HIPC(hipEventRecord(ln.ev_iv[xq], ln.stream));
+      HIPC(hipStreamWaitEvent(os, ln.ev_iv[xq], 0));
     }
-    // new psi of every problem sits in acc(q) = buf[q ? 0 : 2]; outputs j < n_out - 1 of a
-    // multi-output launch in the intermediate accumulators
-    if (any_dist && (rc = dist_exchange(ctx, q ? 0 : 2, 0, ctx->lanes[0].stream))) return rc;
-    if (slot + G.n_out > chunk) {  // the group's outputs share one launch: one chunk
-      if ((rc = flush_partials(ctx, slot, t_flushed, n_t, obs_out, &dist_raw))) return rc;
-      t_flushed += slot;
-      slot = 0;
-    }
-    if (ctx->dbg & 1) {
-      for (int j = 0; j < G.n_out; ++j) {
-        for (auto& ln : ctx->lanes)
-          for (auto& g : ln.groups) {
-            HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
-                            j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
-                            ctx->d_partial + ((slot + j) * ctx->total_items + g.off) * 8, ln.stream,
-                            1, 0, q));
-            if (sites_on)
-              HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
-                                    j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
-                                    ctx->d_site_partial + ((slot + j) * ctx->total_items + g.off) * ctx->site_S,
-                                    ctx->site_S, ln.stream, 1, 0, q));
-            if (pairs_on)
-              HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count,
-                                    j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j,
-                                    ctx->d_pair_partial + ((slot + j) * ctx->total_items + g.off) * ctx->pair_S,
-                                    ctx->pair_S, ln.stream, 1, 0, q));
-          }
-      }
-    } else if ((rc = obs_all(q ? 0 : 2, slot, G.n_out, q))) {
-      return rc;
-    }
-    slot += G.n_out;
-    if (slot == chunk) {
-      if ((rc = flush_partials(ctx, slot, t_flushed, n_t, obs_out, &dist_raw))) return rc;
-      t_flushed += slot;
-      slot = 0;
-    }
-  }
-  phase("launch loop");
-  if (slot > 0) {
-    if ((rc = flush_partials(ctx, slot, t_flushed, n_t, obs_out, &dist_raw))) return rc;
-    t_flushed += slot;
-  }
-  for (size_t li = 0; li < ctx->lanes.size(); ++li)
-    for (int pool = 0; pool < 2; ++pool)
-      if ((rc = drain(ctx->lanes[li], li, pool))) return rc;
-  if ((rc = sync_all(ctx))) return rc;
-  if ((rc = small_gather(ctx, n_t, obs_out))) return rc;
-  phase("flush/drain");
-  if (persistent && any_big) {
-    int herr = 0;
-    HIPC(hipMemcpy(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (herr) return kRcHandoffTimeout;
-  }
-  if (any_dist) {  // sums over all shards of the register, then normalisation (finish_obs)
-    if ((rc = xchg_allreduce_host(ctx, dist_raw.data(), dist_raw.size(), ctx->lanes[0].stream))) return rc;
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-      if (!ctx->probs[pi].dist) continue;
-      for (int ti = 0; ti < n_t; ++ti)
-        finish_obs(ctx->probs[pi], dist_raw.data() + (pi * (size_t)n_t + ti) * 7,
-                   obs_out + pi * DSE_N_OBS * (size_t)n_t + ti, (size_t)n_t);
-    }
-  }
-  phase("tail");
-  ctx->last_q = n_groups & 1;
-  for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
-  ctx->evolved = true;
-  if (ctx->site_obs) ctx->site_nt = n_t;  // the store is complete: dse_get_site_obs may read it
-  if (ctx->pair_obs) {
-    ctx->pair_nt = n_t;
-    ctx->pair_problems = 0;
-    for (const auto& P : ctx->probs) ctx->pair_problems += pair_record(ctx, P) ? 1 : 0;
-  }
-
-  if (stats) {
-    double happl = small_happl + matrix_happl;
-    for (auto& P : ctx->probs)
-      if (!P.side()) happl += (double)P.degree * n_groups;
-    std::memset(stats, 0, sizeof(*stats));
-    stats->h_applications = happl;
-    stats->amplitude_updates = amp_updates;
-    stats->step_bytes = all_bytes;
-    stats->h_flops = all_flops;
-    stats->timed_flops = flops_timed;
-    stats->timed_amp_terms = amps_timed;
-    stats->mode = matrix_pi >= 0 ? 5 : (!any_big ? (any_dense ? 4 : 3) : (persistent ? 1 : (used_wht ? 2 : 0)));
-    int n_dense = 0;
-    for (auto& P : ctx->probs) n_dense += P.dn ? 1 : 0;
-    stats->dense_problems = n_dense;
-    int n_span = 0;
-    for (auto& P : ctx->probs) n_span += P.span_s ? 1 : 0;
-    stats->span_problems = n_span;
-    int n_real = 0;
-    for (auto& P : ctx->probs) n_real += P.rl ? 1 : 0;
-    stats->real_problems = n_real;
-    stats->eig_fallbacks = ctx->eig_fallbacks.load();
-    stats->dense_ms = dense_ms;
-    stats->dense_eig_ms = dense_eig_ms;
-    stats->dense_nufft_problems = any_dense ? ctx->nufft_problems : 0;
-    int n_site = 0;
-    for (const auto& st : ctx->site_store) n_site += st.empty() ? 0 : 1;
-    stats->site_obs_problems = n_site;
-    stats->dense_output_ms = any_dense ? ctx->dense_out_ms : 0.0;
-    int n_custom = 0;  // a loopback partitioned register counts once (its shard 0)
-    for (const auto& P : ctx->probs) n_custom += (P.init_kind && (P.dist || P.shard_rank == 0)) ? 1 : 0;
-    stats->custom_init_problems = n_custom;
-    stats->step_kernel_ms = launches_timed > 0 ? step_ms : -1.0;
-    stats->step_launches = launches + small_launches;
-    stats->timed_launches = launches_timed;
-    stats->timed_bytes = bytes_timed;
-    stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    for (auto& P : ctx->probs)
-      if (P.sm || P.mx) max_deg = std::max(max_deg, P.degree);
-    stats->max_degree = max_deg;
-    stats->n_intervals = n_t - 1;
-    stats->tile_bits = ctx->probs.empty() ? 0 : ctx->probs.front().L;
-    stats->streams = n_lanes;
-    stats->outputs_per_launch = M;
-    stats->handoff_fallbacks = ctx->handoff_fallbacks;
-    stats->exchange_bytes = ctx->xbytes;
-    if ((rc = xt_sum(ctx))) return rc;
-    stats->exchange_ms = ctx->xms;
-    stats->lane0_kernel_ms = lane0_ms;
-    stats->lane0_launches = lane0_launches;
-    stats->lane0_amp_terms = lane0_amps;
-    if (matrix_pi >= 0) {
-      stats->matrix_build_ms = ctx->mx_build_ms;
-      stats->matrix_products_ms = ctx->mx_products_ms;
-      stats->matrix_products = ctx->mx_products;
-      stats->matrix_bytes_per_product = ctx->mx_bytes_per_product;
+    for (auto& g : ln.groups)
+      if (int rc = launch_group_obs(ctx, g, bsel_q, slot, n_out, 1, xq, os)) return rc;
+    if (pl.obs_ovl) {
+      HIPC(hipEventRecord(ln.ev_obs[xq], os));
+      ln.obs_pending[xq] = true;
     }
   }
   return DSE_OK;
 }
+
+// Persistent: all K terms of the intervals of G in one launch of lane group g; 2-tile groups in
+// co-resident chunks of cap items; mixed groups in one launch; spanning registers in one k_span
+// launch per chunk of span_cuts (each chunk's registers' tiles all resident at once: the cuts are
+// sized to the chip's resident capacity), flags zeroed first
+int launch_persistent_group(dse_ctx* ctx, EvolvePlan& pl, Lane& ln, size_t li, LaneGroup& g,
+                                   const IntervalGroup& G, int gi) {
+  const int T = 1 << g.L, q = gi & 1, pool = gi & 1, set = G.set;
+  const bool timed = ctx->time_every > 0 && (gi % ctx->time_every) == 0;
+  const bool span = g.kind == GroupKind::Span, real = g.kind == GroupKind::Real;
+  if (span) HIPC(hipMemsetAsync(ctx->d_span_flags.p, 0, ctx->d_span_flags.cap * sizeof(int), ln.stream));
+  else if (g.kind == GroupKind::Mixed || (g.kind == GroupKind::Tiles && g.tiles != 1))
+    HIPC(zero_flags(ctx->d_items + g.off, (int)g.count, ctx->d_flags.p, ln.stream));
+  auto launch_g = [&](int64_t off, int cnt) -> hipError_t {
+    if (real)
+      return launch_real(ctx->d_probs, ctx->d_real_items.p + g.real_off, (int)g.real_count, set, G.n_out, ln.stream);
+    if (span)  // chunk [off, off + cnt) of the group's span launches
+      return launch_span(g.span_L, g.span_rb, pl.imag_all, ctx->d_probs, ctx->d_span.p,
+                         ctx->d_span_items.p + g.span_off + g.span_cuts[off],
+                         (int)(g.span_cuts[off + cnt] - g.span_cuts[off]), q, set, G.n_out, pl.d_err, ctx->hk,
+                         ln.stream);
+    return launch_interval(g.L, pl.imag_all, ctx->d_probs, ctx->d_items_iv + g.off + off, cnt, q, set, G.n_out,
+                           ctx->d_flags.p, pl.d_err, ctx->hk, ln.stream);
+  };
+  // span: off / cnt count chunks of span_cuts, not items
+  const int64_t gcap = span ? 1 : (g.kind == GroupKind::Tiles && g.tiles == 2) ? pl.cap : g.count;
+  const int64_t gn = span ? (int64_t)g.span_cuts.size() - 1 : g.count;
+  for (int64_t off = 0; off < gn; off += gcap) {
+    const int cnt = (int)std::min<int64_t>(gcap, gn - off);
+    double fl = 0.0, am = 0.0;
+    if (span) {  // the chunk's registers
+      am = g.span_am[off];
+      fl = g.span_fl[off];
+    } else {
+      for (int64_t i = off; i < off + cnt; ++i) {
+        const HostProblem& P = ctx->probs[pl.items[g.off + i].x];
+        am += (double)T * P.degree;
+        fl += (double)T * P.degree * P.flops_per_amp;
+      }
+    }
+    if (int rc = pl.timer.run(ctx, ln, li, pool, timed, {fl, 0.0, am}, [&]() -> int {
+          HIPC(launch_g(off, cnt));
+          return DSE_OK;
+        }))
+      return rc;
+    pl.launches += 1.0;
+    pl.amp_updates += am;
+    pl.all_flops += fl;
+  }
+  // real-component registers: psi of every output (computational frame) and the next [a | b]
+  if (real)
+    HIPC(launch_real_combine(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, q, G.n_out, ln.stream));
+  return DSE_OK;
+}
+
+// Streaming: the interval of G term by term, one launch of the step kernels or one pass set of the
+// Walsh-Hadamard engine per term over the items still active
+int launch_streaming_group(dse_ctx* ctx, EvolvePlan& pl, Lane& ln, size_t li, LaneGroup& g,
+                                  const IntervalGroup& G, int gi) {
+  const int T = 1 << g.L, q = gi & 1, pool = gi & 1, set = G.set;
+  const bool timed = ctx->time_every > 0 && (gi % ctx->time_every) == 0;
+  int rc;
+  if (pl.any_dist_step && (rc = dist_exchange(ctx, q ? 2 : 0, 1, ln.stream))) return rc;
+  // fused FINAL + FIRST for the whole evolve, or not at all: a group with any partitioned
+  // register (index swaps around MID) runs unfused, also on the terms past that register's degree
+  const bool fuse = ctx->wht_fuse && g.wht_regs.empty();
+  auto step = [&](int mode, int na, int k) -> int {
+    if (g.wht_groups) {
+      std::vector<int> regs;
+      for (const auto& rg : g.wht_regs)
+        if (rg.second >= k) regs.push_back(rg.first);
+      return wht_run(ctx, g.L, g.wht_groups, {{ctx->d_items + g.off, na}}, regs, fuse, mode, k, q, set,
+                     ln.stream);
+    }
+    HIPC(launch_step(g.L, mode, ctx->d_probs, ctx->d_items + g.off, na, k, q, set, ln.stream));
+    return DSE_OK;
+  };
+  if ((rc = step(MODE_FIRST, g.active[1], 1))) return rc;
+  for (int k = 2; k < (int)g.active.size(); ++k) {
+    const int na = g.active[k];
+    if (na <= 0) break;
+    if (pl.any_dist_step && (rc = dist_exchange(ctx, ((k - 1) & 1) ? 1 : (q ? 2 : 0), k, ln.stream))) return rc;
+    if ((rc = pl.timer.run(ctx, ln, li, pool, timed, {g.flops[k], g.bytes[k], (double)na * T},
+                           [&]() { return step(MODE_GEN, na, k); })))
+      return rc;
+    pl.launches += 1.0;
+    pl.amp_updates += (double)na * T;
+    pl.all_bytes += g.bytes[k];
+    pl.all_flops += g.flops[k];
+  }
+  return DSE_OK;
+}
+
+int flush_slots(dse_ctx* ctx, EvolvePlan& pl) {
+  if (int rc = flush_partials(ctx, pl.slot, pl.t_flushed, pl.n_t, pl.obs_out, &pl.dist_raw)) return rc;
+  pl.t_flushed += pl.slot;
+  pl.slot = 0;
+  return DSE_OK;
+}
+
+// observables of psi(t0), then per group of intervals: every lane's launches, the observables of
+// the group's outputs, a flush when the arenas are full
+int run_intervals(dse_ctx* ctx, EvolvePlan& pl) {
+  int rc;
+  pl.timer.recs.assign(ctx->lanes.size() * 2, {});
+  for (auto& ln : ctx->lanes) ln.obs_pending[0] = ln.obs_pending[1] = false;
+  pl.dist_raw.assign(pl.any_dist ? ctx->probs.size() * (size_t)pl.n_t * 7 : 0, 0.0);
+  if (pl.any_dist && (rc = dist_exchange(ctx, 0, 0, ctx->lanes[0].stream))) return rc;
+  if ((rc = launch_all_obs(ctx, pl, 0, pl.slot++, 1, 1))) return rc;
+  for (int gi = 0; gi < (int)pl.groups.size(); ++gi) {
+    const IntervalGroup& G = pl.groups[gi];
+    const int q = gi & 1;
+    for (size_t li = 0; li < ctx->lanes.size(); ++li) {
+      Lane& ln = ctx->lanes[li];
+      if (ln.groups.empty()) continue;
+      if ((rc = pl.timer.drain(ctx, ln, li, q))) return rc;
+      if (pl.obs_ovl && ln.obs_pending[q]) {  // the observables that read what this group rewrites
+        HIPC(hipStreamWaitEvent(ln.stream, ln.ev_obs[q], 0));
+        ln.obs_pending[q] = false;
+      }
+      for (auto& g : ln.groups)
+        if ((rc = pl.persistent ? launch_persistent_group(ctx, pl, ln, li, g, G, gi)
+                                : launch_streaming_group(ctx, pl, ln, li, g, G, gi)))
+          return rc;
+    }
+    // new psi of every problem sits in acc(q) = buf[q ? 0 : 2]; outputs j < n_out - 1 of a
+    // multi-output launch in the intermediate accumulators
+    if (pl.any_dist && (rc = dist_exchange(ctx, q ? 0 : 2, 0, ctx->lanes[0].stream))) return rc;
+    // the group's outputs share one launch: one chunk
+    if (pl.slot + G.n_out > pl.chunk && (rc = flush_slots(ctx, pl))) return rc;
+    if (ctx->dbg & 1) {  // one output per launch, on the lanes' own streams
+      for (int j = 0; j < G.n_out; ++j)
+        for (auto& ln : ctx->lanes)
+          for (auto& g : ln.groups)
+            if ((rc = launch_group_obs(ctx, g, j == G.n_out - 1 ? (q ? 0 : 2) : 3 + j, pl.slot + j, 1, 0, q, ln.stream)))
+              return rc;
+    } else if ((rc = launch_all_obs(ctx, pl, q ? 0 : 2, pl.slot, G.n_out, q))) {
+      return rc;
+    }
+    pl.slot += G.n_out;
+    if (pl.slot == pl.chunk && (rc = flush_slots(ctx, pl))) return rc;
+  }
+  pl.phase("launch loop");
+  return DSE_OK;
+}
+
+// the last flush, the timing events, every stream, the small engine's results, the hand-off error
+// word, the sums of the registers partitioned over processes; then the context's record of the call
+int finish_evolve(dse_ctx* ctx, EvolvePlan& pl) {
+  int rc;
+  if (pl.slot > 0 && (rc = flush_slots(ctx, pl))) return rc;
+  for (size_t li = 0; li < ctx->lanes.size(); ++li)
+    for (int pool = 0; pool < 2; ++pool)
+      if ((rc = pl.timer.drain(ctx, ctx->lanes[li], li, pool))) return rc;
+  if ((rc = sync_all(ctx))) return rc;
+  if ((rc = small_gather(ctx, pl.n_t, pl.obs_out))) return rc;
+  pl.phase("flush/drain");
+  if (pl.persistent && pl.any_big) {
+    int herr = 0;
+    HIPC(hipMemcpy(&herr, pl.d_err, sizeof(int), hipMemcpyDeviceToHost));
+    if (herr) return kRcHandoffTimeout;
+  }
+  if (pl.any_dist) {  // sums over all shards of the register, then normalisation (finish_obs)
+    if ((rc = xchg_allreduce_host(ctx, pl.dist_raw.data(), pl.dist_raw.size(), ctx->lanes[0].stream))) return rc;
+    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+      if (!ctx->probs[pi].dist) continue;
+      for (int ti = 0; ti < pl.n_t; ++ti)
+        finish_obs(ctx->probs[pi], pl.dist_raw.data() + (pi * (size_t)pl.n_t + ti) * 7,
+                   pl.obs_out + pi * DSE_N_OBS * (size_t)pl.n_t + ti, (size_t)pl.n_t);
+    }
+  }
+  pl.phase("tail");
+  ctx->last_q = (int)pl.groups.size() & 1;
+  for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
+  ctx->evolved = true;
+  if (ctx->site_obs) ctx->site_nt = pl.n_t;  // the store is complete: dse_get_site_obs may read it
+  if (ctx->pair_obs) {
+    ctx->pair_nt = pl.n_t;
+    ctx->pair_problems = 0;
+    for (const auto& P : ctx->probs) ctx->pair_problems += pair_record(ctx, P) ? 1 : 0;
+  }
+  return DSE_OK;
+}
+
+int fill_stats(dse_ctx* ctx, const EvolvePlan& pl, dse_stats* stats) {
+  const LaunchTimer& tm = pl.timer;
+  double happl = pl.small_happl + pl.matrix_happl;
+  int n_dense = 0, n_span = 0, n_real = 0, n_custom = 0, max_deg = pl.max_deg;
+  for (const auto& P : ctx->probs) {
+    if (!P.side()) happl += (double)P.degree * (int)pl.groups.size();
+    n_dense += P.dn ? 1 : 0;
+    n_span += P.span_s ? 1 : 0;
+    n_real += P.rl ? 1 : 0;
+    // a loopback partitioned register counts once (its shard 0)
+    n_custom += (P.init_kind && (P.dist || P.shard_rank == 0)) ? 1 : 0;
+    if (P.sm || P.mx) max_deg = std::max(max_deg, P.degree);
+  }
+  int n_site = 0;
+  for (const auto& st : ctx->site_store) n_site += st.empty() ? 0 : 1;
+  std::memset(stats, 0, sizeof(*stats));
+  stats->h_applications = happl;
+  stats->amplitude_updates = pl.amp_updates;
+  stats->step_bytes = pl.all_bytes;
+  stats->h_flops = pl.all_flops;
+  stats->timed_flops = tm.flops;
+  stats->timed_amp_terms = tm.amp_terms;
+  stats->mode = pl.matrix_pi >= 0 ? 5 : (!pl.any_big ? (pl.any_dense ? 4 : 3) : (pl.persistent ? 1 : (pl.used_wht ? 2 : 0)));
+  stats->dense_problems = n_dense;
+  stats->span_problems = n_span;
+  stats->real_problems = n_real;
+  stats->eig_fallbacks = ctx->eig_fallbacks.load();
+  stats->dense_ms = pl.dense_ms;
+  stats->dense_eig_ms = pl.dense_eig_ms;
+  stats->dense_nufft_problems = pl.any_dense ? ctx->nufft_problems : 0;
+  stats->site_obs_problems = n_site;
+  stats->dense_output_ms = pl.any_dense ? ctx->dense_out_ms : 0.0;
+  stats->custom_init_problems = n_custom;
+  stats->step_kernel_ms = tm.launches > 0 ? tm.step_ms : -1.0;
+  stats->step_launches = pl.launches + pl.small_launches;
+  stats->timed_launches = tm.launches;
+  stats->timed_bytes = tm.bytes;
+  stats->wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pl.wall0).count();
+  stats->max_degree = max_deg;
+  stats->n_intervals = pl.n_t - 1;
+  stats->tile_bits = ctx->probs.empty() ? 0 : ctx->probs.front().L;
+  stats->streams = pl.n_lanes;
+  stats->outputs_per_launch = pl.M;
+  stats->handoff_fallbacks = ctx->handoff_fallbacks;
+  stats->exchange_bytes = ctx->xbytes;
+  if (int rc = xt_sum(ctx)) return rc;
+  stats->exchange_ms = ctx->xms;
+  stats->lane0_kernel_ms = tm.lane0_ms;
+  stats->lane0_launches = tm.lane0_launches;
+  stats->lane0_amp_terms = tm.lane0_amp_terms;
+  if (pl.matrix_pi >= 0) {
+    stats->matrix_build_ms = ctx->mx_build_ms;
+    stats->matrix_products_ms = ctx->mx_products_ms;
+    stats->matrix_products = ctx->mx_products;
+    stats->matrix_bytes_per_product = ctx->mx_bytes_per_product;
+  }
+  return DSE_OK;
+}
+
+int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_out, dse_stats* stats) {
+  EvolvePlan pl;
+  pl.t = t, pl.n_t = n_t, pl.tol = tol, pl.obs_out = obs_out;
+  pl.wall0 = pl.tmark = std::chrono::steady_clock::now();
+  int rc;
+  if ((rc = check_times(ctx, pl))) return rc;
+  HIPC(hipSetDevice(ctx->device));
+  // timing-event records of an earlier call that ended early (an error, or the hand-off timeout
+  // dse_evolve re-runs) are dropped: their per-launch counters lived in that call
+  for (auto& ln : ctx->lanes) ln.ev_used[0] = ln.ev_used[1] = 0;
+  if ((rc = prepare(ctx))) return rc;
+  ctx->xbytes = 0.0;
+  ctx->xms = 0.0;
+  ctx->xev_used = 0;
+  pl.phase("prepare");
+  if ((rc = choose_engines(ctx, pl))) return rc;
+  choose_span(ctx, pl);
+  choose_real(ctx, pl);
+  if ((rc = choose_wht(ctx, pl))) return rc;
+  choose_outputs_per_launch(ctx, pl);
+  if ((rc = group_intervals(ctx, pl))) return rc;
+  pl.phase("groups");
+  if ((rc = build_coefficients(ctx, pl))) return rc;
+  if ((rc = place_output_buffers(ctx, pl)) || (rc = place_handoff_buffers(ctx, pl))) return rc;
+  if ((rc = assign_lanes(ctx, pl))) return rc;
+  if (pl.persistent) {
+    if ((rc = order_interval_items(ctx, pl)) || (rc = order_span_items(ctx, pl))) return rc;
+    order_real_items(ctx, pl);
+  }
+  if ((rc = upload_items_and_flags(ctx, pl))) return rc;
+  pl.phase("lanes/items");
+  if ((rc = write_initial_states(ctx, pl)) || (rc = run_side_engines(ctx, pl))) return rc;
+  pl.phase("psi0/small");
+  if ((rc = size_obs_chunks(ctx, pl)) || (rc = run_intervals(ctx, pl)) || (rc = finish_evolve(ctx, pl))) return rc;
+  return stats ? fill_stats(ctx, pl, stats) : DSE_OK;
+}
+
+}  // namespace
+
+extern "C" {
 
 int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_out, dse_stats* stats) {
   if (!ctx) return DSE_ERR_ARG;

@@ -139,3 +139,89 @@ int main() {
     assert res.returncode == 0, res.stderr[-2000:]
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert run.returncode == 0 and run.stdout.strip() == "ok", (run.returncode, run.stdout, run.stderr)
+
+
+CHEB_ROWS_SRC = r'''
+#include "dse_internal.h"
+#include "dse.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <vector>
+int main() {
+  const double alphas[3] = {std::max(0.0, 1e-300), 3e4, 2e6};  // 0 as coef_one clamps it
+  const double beta = 1.5e5, tol = 1e-14;
+  const int M = 4;
+  const std::vector<std::vector<double>> sets = {{1e-5}, {1e-5, 2e-5}, {2.5e-4, 5e-4, 7.5e-4, 1e-3}};
+  const long double pi = 3.141592653589793238462643383279502884L;
+  double worst = 0.0;
+  for (double alpha : alphas) {
+    int deg = 0, over = 0;
+    std::vector<std::pair<double, double>> rows;
+    if (dse::cheb_rows(alpha, beta, sets, M, tol, 2e6, &deg, &rows, &over) != DSE_OK) return 1;
+    const size_t w = (size_t)deg + 2;  // kcap1 + 1
+    if (rows.size() != sets.size() * M * w) return 2;
+    int dmax = 1;
+    for (size_t s = 0; s < sets.size(); ++s)
+      for (int j = 0; j < M; ++j) {
+        const std::pair<double, double>* row = rows.data() + (s * M + j) * w;
+        if (j >= (int)sets[s].size()) {  // a set shorter than M: zero-filled rows
+          for (size_t e = 0; e < w; ++e)
+            if (row[e].first != 0.0 || row[e].second != 0.0) return 3;
+          continue;
+        }
+        const double tau = sets[s][j], z = alpha * tau;
+        const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
+        std::vector<double> J(kmax + 1);
+        int d = 0;
+        if (dse_bessel_j(z, kmax, J.data(), tol, &d) != DSE_OK) return 4;
+        if (row[0].first != (double)d || row[0].second != 0.0) return 5;  // (a)
+        dmax = std::max(dmax, d);
+        for (size_t k = (size_t)d + 1; k + 1 < w; ++k)  // (c)
+          if (row[1 + k].first != 0.0 || row[1 + k].second != 0.0) return 6;
+        for (int i = 0; i < 33; ++i) {  // (d)
+          const long double x = std::cos(pi * (i + 0.5L) / 33.0L);
+          long double t0 = 1.0L, t1 = x, re = row[1].first, im = row[1].second;
+          for (int k = 1; k <= d; ++k) {
+            re += row[1 + k].first * t1;
+            im += row[1 + k].second * t1;
+            const long double t2 = 2.0L * x * t1 - t0;
+            t0 = t1;
+            t1 = t2;
+          }
+          const long double ph = -((long double)alpha * x + (long double)beta) * (long double)tau;
+          const double err = (double)std::hypot(re - std::cos(ph), im - std::sin(ph));
+          worst = std::max(worst, err);
+          if (!(err <= 1e-12)) {
+            std::printf("alpha %g tau %g x %g: error %.3e\n", alpha, tau, (double)x, err);
+            return 7;
+          }
+        }
+      }
+    if (deg != dmax) return 8;  // (b)
+  }
+  std::printf("ok %.3e\n", worst);
+  return 0;
+}
+'''
+
+
+def test_cheb_rows_match_bessel_and_the_propagator(tmp_path):
+    """cheb_rows (dse_host.cpp: the coefficient rows every Chebyshev engine of dse_evolve uploads) for a
+    zero, a moderate and a stiff spectral half-width (z = alpha tau up to 2000), M = 4 with sets shorter
+    than M: every row's degree is dse_bessel_j's, deg their maximum, the entries past a row's degree
+    and the rows past a set's length are zero, and at 33 Chebyshev nodes sum_k a_k T_k(x) is
+    exp(-i (alpha x + beta) tau) to 1e-12.  The bound: the dropped tail is below ~tol = 1e-14, and at
+    most ~2,100 terms of magnitude <= 2, each coefficient rounded in fp64, sum to an error of at most
+    2,100 * 2 * 2.2e-16 ~ 1e-12.  T_k by the three-term recurrence, carried with the reference phase
+    in long double, so the figure is the rows' error and not the recurrence's."""
+    src = tmp_path / "rows.cpp"
+    src.write_text(CHEB_ROWS_SRC)
+    exe = tmp_path / "rows"
+    res = subprocess.run([_hipcc(), "-std=c++17", "-I", CSRC, "-I", os.path.join(ROOT, "include"),
+                          "-x", "hip", "--offload-arch=gfx950", str(src), os.path.join(CSRC, "dse_host.cpp"),
+                          "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout)
+    assert run.returncode == 0 and run.stdout.startswith("ok"), (run.returncode, run.stdout, run.stderr)
