@@ -135,6 +135,33 @@ struct DevBuf {
 template <class... B>
 void release_all(B&... b) { (b.release(), ...); }
 
+// The observable families beside the seven aggregates: sums per unit (register bit, pair of bits)
+// of every output state, kept per register and read back after the evolve.  kObsFamilies below
+// describes each; the engines launch them in this order and read them back in the reverse one.
+enum ObsFamily { kSite = 0, kPair = 1, kNumObsFamilies = 2 };
+constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair};
+constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kPair, kSite};
+
+// What a context holds for one family: its option, a partial arena for the tile engine's kernel
+// (S doubles per tile and slot: the family's stride of the context's widest register), and the
+// results of the last evolve, per register [comps][units][n_t] (loopback group: shard 0's entry)
+struct ObsFamilyState {
+  int on = 0;
+  DevBuf<double> d_partial;
+  size_t slots = 0;
+  int S = 0;
+  std::vector<std::vector<double>> store;
+  int nt = 0;              // output times of store (0: none)
+  int problems = 0;        // registers with sums in the last successful evolve
+  DevBuf<double> d_small;  // small engine: [problem][n_t][small_stride] raw sums
+  void release() {
+    release_all(d_partial, d_small);
+    slots = 0;
+    store.clear();
+    nt = problems = 0;
+  }
+};
+
 // What a lane group launches.  Tiles: k_interval (persistent) or the step / Walsh-Hadamard kernels (streaming)
 // over problems of `tiles` tiles each; Mixed: 1- and 2-tile problems in one k_interval launch; Span: k_span; Real: k_real
 enum class GroupKind { Tiles, Mixed, Span, Real };
@@ -196,27 +223,8 @@ struct dse_ctx {
   int64_t total_items = 0;
   DevBuf<double> d_partial;
   size_t partial_slots = 0;
-  // site-resolved observables (option "site_obs", dse_site_observables): a second partial arena for
-  // k_obs_sites, site_S doubles per tile and slot (site_stride of the context's widest register),
-  // and the results of the last evolve, per register [3][n][n_t] (loopback group: shard 0's entry)
-  int site_obs = 0;
-  DevBuf<double> d_site_partial;
-  size_t site_slots = 0;
-  int site_S = 0;
-  std::vector<std::vector<double>> site_store;
-  int site_nt = 0;                  // output times of site_store (0: none)
-  DevBuf<double> d_small_sites;      // small engine: [problem][n_t][kSmallSiteStride] raw site sums
-  // two-spin correlators (option "pair_obs", dse_pair_observables): a third partial arena for
-  // k_obs_pairs, pair_S doubles per tile and slot (pair_stride of the context's widest register),
-  // and the results of the last evolve, per register [5][NP][n_t] (loopback group: shard 0's entry)
-  int pair_obs = 0;
-  DevBuf<double> d_pair_partial;
-  size_t pair_slots = 0;
-  int pair_S = 0;
-  std::vector<std::vector<double>> pair_store;
-  int pair_nt = 0;                  // output times of pair_store (0: none)
-  int pair_problems = 0;            // registers with pair sums in the last successful evolve
-  DevBuf<double> d_small_pairs;      // small engine: [problem][n_t][kSmallPairStride] raw pair sums
+  // site-resolved observables and two-spin correlators (kObsFamilies), indexed by ObsFamily
+  ObsFamilyState fam[kNumObsFamilies];
   std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
   bool prepared = false;
   bool evolved = false;
@@ -507,14 +515,10 @@ void free_device(dse_ctx* ctx) {
   if (ctx->d_probs) (void)hipFree(ctx->d_probs), ctx->d_probs = nullptr;
   if (ctx->d_items) (void)hipFree(ctx->d_items), ctx->d_items = nullptr;
   if (ctx->d_items_iv) (void)hipFree(ctx->d_items_iv), ctx->d_items_iv = nullptr;
-  release_all(ctx->d_partial, ctx->d_site_partial, ctx->d_pair_partial, ctx->d_small_sites, ctx->d_small_pairs,
-              ctx->d_flags, ctx->d_xslots, ctx->d_xacc, ctx->d_real, ctx->d_real_tab, ctx->d_real_items, ctx->d_span,
-              ctx->d_span_tab, ctx->d_span_slots, ctx->d_span_flags, ctx->d_span_items, ctx->d_coef, ctx->d_sm_coef,
-              ctx->d_init, ctx->d_small, ctx->d_small_out, ctx->d_small_aux, ctx->d_allreduce);
-  ctx->site_slots = ctx->pair_slots = 0;
-  ctx->site_store.clear();
-  ctx->pair_store.clear();
-  ctx->site_nt = ctx->pair_nt = ctx->pair_problems = 0;
+  release_all(ctx->d_partial, ctx->fam[kSite], ctx->fam[kPair], ctx->d_flags, ctx->d_xslots, ctx->d_xacc, ctx->d_real,
+              ctx->d_real_tab, ctx->d_real_items, ctx->d_span, ctx->d_span_tab, ctx->d_span_slots, ctx->d_span_flags,
+              ctx->d_span_items, ctx->d_coef, ctx->d_sm_coef, ctx->d_init, ctx->d_small, ctx->d_small_out,
+              ctx->d_small_aux, ctx->d_allreduce);
   for (auto& kv : ctx->zzlo_tables) (void)hipFree(kv.second);
   ctx->zzlo_tables.clear();
   ctx->partial_slots = 0;
@@ -1208,117 +1212,121 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
   return DSE_OK;
 }
 
-// the second arena, for k_obs_sites: slots x total_items x S doubles, S = site_stride of the widest
-// register of the context
-int ensure_site_partial(dse_ctx* ctx, size_t slots) {
-  const int S = site_stride(widest_register(ctx));
-  if (ctx->site_slots >= slots && ctx->site_S == S) return DSE_OK;
-  ctx->site_slots = 0;
-  ctx->d_site_partial.release();
-  if (int rc = ctx->d_site_partial.reserve(ctx, slots * ctx->total_items * S,
-                                           "device allocation of site-observable partials failed"))
-    return rc;
-  ctx->site_slots = slots;
-  ctx->site_S = S;
-  return DSE_OK;
-}
+// ---- observable families: site-resolved observables and two-spin correlators ------------------
 
-// raw site sums v (X_b Y_b Z_b at [3 b + c], ||psi||^2 at [3 n]) of an n-qubit register, normalised
-// into o[c][b] at o[(c * n + b) * stride]
-void finish_sites(int n, const double* v, double* o, size_t stride) {
-  const double n2 = v[3 * n];
-  const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
-  for (int b = 0; b < n; ++b)
-    for (int c = 0; c < 3; ++c) o[((size_t)c * n + b) * stride] = v[3 * b + c] * inv;
-}
+// One family: raw sums v of a register, comps per unit at v[comps * u + c] and ||psi||^2 at
+// v[comps * units], `stride` doubles per state; results normalised by that norm.
+struct ObsFamilyDesc {
+  const char *option, *hook, *noun;  // the option's and the hook's names, the family's word in messages
+  int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index)
+  int (*units)(int n);
+  int (*stride)(int n);
+  int small_stride;                                        // the small engine's stride (its widest register's)
+  decltype(&launch_obs_sites) launch;                      // tile engine: S >= stride(n) doubles per tile
+  decltype(&launch_dense_obs_sites) launch_dense;          // dense engine, batched
+  decltype(&launch_dense_obs_sites_c) launch_dense_c;      // dense engine and matrix mode: one register, interleaved columns
+  double* DenseProb::*dense_out;                           // where those two write
+  // Where the twins differ.  The site hook refuses only its own register when that is a dist shard,
+  // before prepare; the pair hook refuses as the option does (obs_family_refusal), after it
+  bool hook_refuses_shard_early;
+  // refusal when one output slot of the arena exceeds kPartialCapBytes (pair: up to 2806 doubles per
+  // tile; the site arena, at most 104 per tile, takes one slot per flush then)
+  bool slot_cap;
+  bool get_needs_option;  // the getter refuses once the option is back at 0 (site: serves the last record)
+};
+const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
+    {"site_obs", "dse_site_observables", "site", 3, [](int n) { return n; }, [](int n) { return site_stride(n); },
+     kSmallSiteStride, launch_obs_sites, launch_dense_obs_sites, launch_dense_obs_sites_c, &DenseProb::sites, true, false, false},
+    {"pair_obs", "dse_pair_observables", "pair", 5, [](int n) { return n * (n - 1) / 2; },
+     [](int n) { return pair_stride(n); }, kSmallPairStride, launch_obs_pairs, launch_dense_obs_pairs,
+     launch_dense_obs_pairs_c, &DenseProb::pairs, false, true, true},
+};
 
-// A fresh store for this evolve (dse_evolve has already marked the old one invalid, site_nt = 0; it
-// becomes readable again only when the evolve succeeds).  The re-run after a hand-off timeout starts over as well (its
-// results overwrite the first pass's), except for the dense registers, whose first-pass results
-// are kept like their aggregates (dense_run is not repeated).
-void reset_site_store(dse_ctx* ctx, int n_t) {
-  ctx->site_store.resize(ctx->probs.size());
-  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-    const HostProblem& P = ctx->probs[pi];
-    std::vector<double>& st = ctx->site_store[pi];
-    const size_t want = ctx->site_obs && !(P.shard_bits > 0 && P.shard_rank != 0) ? (size_t)3 * P.n * n_t : 0;
-    if (ctx->rerun && P.dn && st.size() == want) continue;
-    st.assign(want, 0.0);  // (a loopback group's sums live in shard 0's entry)
-  }
-}
-
-// ---- two-spin correlators (option pair_obs): the third arena and its host store ---------------
-
-// Refusals of the option and of the hook, decided before any work (after prepare: the tile count is
-// known): no register partitioned over processes, and one output slot of the arena, tiles x
-// pair_stride(n_max) doubles, within the cap of the other arenas
-int pair_refusal(dse_ctx* ctx, const char* who) {
+// Refusals of the option and of the hook (`who`), decided before any work (after prepare: the tile
+// count is known): no register partitioned over processes, and with slot_cap one output slot of the
+// arena, tiles x stride(n_max) doubles, within the cap of the other arenas
+int obs_family_refusal(dse_ctx* ctx, ObsFamily f, const char* who) {
+  const ObsFamilyDesc& F = kObsFamilies[f];
   for (const auto& P : ctx->probs)
     if (P.dist)
-      return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over "
-                                        "processes (the all-reduce of the pair sums is not implemented)");
-  const int64_t per_slot = ctx->total_items * (int64_t)pair_stride(widest_register(ctx)) * 8;
-  if (per_slot > kPartialCapBytes)
-    return fail(ctx, DSE_ERR_ARG, std::string(who) + ": the pair sums of one output (" + std::to_string(ctx->total_items) +
-                                      " tiles x " + std::to_string(pair_stride(widest_register(ctx))) +
+      return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over processes "
+                                        "(the all-reduce of the " + F.noun + " sums is not implemented)");
+  const int S = F.stride(widest_register(ctx));
+  if (F.slot_cap && ctx->total_items * (int64_t)S * 8 > kPartialCapBytes)
+    return fail(ctx, DSE_ERR_ARG, std::string(who) + ": the " + F.noun + " sums of one output (" +
+                                      std::to_string(ctx->total_items) + " tiles x " + std::to_string(S) +
                                       " doubles) exceed the 256 MiB partial arena");
   return DSE_OK;
 }
 
-// slots x total_items x S doubles, S = pair_stride of the widest register of the context
-int ensure_pair_partial(dse_ctx* ctx, size_t slots) {
-  const int S = pair_stride(widest_register(ctx));
-  if (ctx->pair_slots >= slots && ctx->pair_S == S) return DSE_OK;
-  ctx->pair_slots = 0;
-  ctx->d_pair_partial.release();
-  if (int rc = ctx->d_pair_partial.reserve(ctx, slots * std::max<int64_t>(1, ctx->total_items) * S,
-                                           "device allocation of pair-observable partials failed"))
-    return rc;
-  ctx->pair_slots = slots;
-  ctx->pair_S = S;
+// the family's arena: slots x total_items x S doubles, S = its stride of the widest register of the
+// context (total_items >= 1: prepare refuses an empty context)
+int ensure_family_partial(dse_ctx* ctx, ObsFamily f, size_t slots) {
+  ObsFamilyState& A = ctx->fam[f];
+  const int S = kObsFamilies[f].stride(widest_register(ctx));
+  if (A.slots >= slots && A.S == S) return DSE_OK;
+  A.slots = 0;
+  A.d_partial.release();
+  const std::string what = std::string("device allocation of ") + kObsFamilies[f].noun + "-observable partials failed";
+  if (int rc = A.d_partial.reserve(ctx, slots * ctx->total_items * S, what.c_str())) return rc;
+  A.slots = slots;
+  A.S = S;
   return DSE_OK;
 }
 
-// raw pair sums v (ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at [5 p + c], ||psi||^2 at [5 NP]) of an
-// n-qubit register, normalised into o[c][p] at o[(c * NP + p) * stride]
-void finish_pairs(int n, const double* v, double* o, size_t stride) {
-  const int np = n * (n - 1) / 2;
-  const double n2 = v[5 * np];
+// raw sums v of an n-qubit register, normalised into o[c][u] at o[(c * units + u) * stride]
+void finish_family(const ObsFamilyDesc& F, int n, const double* v, double* o, size_t stride) {
+  const int units = F.units(n);
+  const double n2 = v[F.comps * units];
   const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
-  for (int p = 0; p < np; ++p)
-    for (int c = 0; c < 5; ++c) o[((size_t)c * np + p) * stride] = v[5 * p + c] * inv;
+  for (int u = 0; u < units; ++u)
+    for (int c = 0; c < F.comps; ++c) o[((size_t)c * units + u) * stride] = v[F.comps * u + c] * inv;
 }
 
-size_t pair_store_size(const HostProblem& P, int n_t) { return (size_t)5 * (P.n * (P.n - 1) / 2) * n_t; }
+// finish_family for register pi's outputs 0 .. n_t - 1, raw sums `stride` doubles apart, into its store
+void finish_family_outputs(dse_ctx* ctx, ObsFamily f, size_t pi, const double* raw, size_t stride, int n_t) {
+  for (int ti = 0; ti < n_t; ++ti)
+    finish_family(kObsFamilies[f], ctx->probs[pi].n, raw + ti * stride, ctx->fam[f].store[pi].data() + ti, (size_t)n_t);
+}
+
+size_t obs_store_size(ObsFamily f, const HostProblem& P, int n_t) {
+  return (size_t)kObsFamilies[f].comps * kObsFamilies[f].units(P.n) * n_t;
+}
 // which registers keep a record (a loopback group's sums live in shard 0's entry)
-bool pair_record(const dse_ctx* ctx, const HostProblem& P) {
-  return ctx->pair_obs && !(P.shard_bits > 0 && P.shard_rank != 0);
+bool obs_record(const dse_ctx* ctx, ObsFamily f, const HostProblem& P) {
+  return ctx->fam[f].on && !(P.shard_bits > 0 && P.shard_rank != 0);
 }
+// registers with a record from the last evolve (0 unless it succeeded with the option on)
+int obs_family_problems(const dse_ctx* ctx, ObsFamily f) { return ctx->fam[f].nt > 0 ? ctx->fam[f].problems : 0; }
 
-// A fresh store for this evolve, under reset_site_store's rules (the re-run after a hand-off
-// timeout starts over, except for the dense registers' first-pass results)
-void reset_pair_store(dse_ctx* ctx, int n_t) {
-  ctx->pair_store.resize(ctx->probs.size());
+// A fresh store for this evolve (dse_evolve has already marked the old one invalid, nt = 0; it
+// becomes readable again only when the evolve succeeds).  The re-run after a hand-off timeout starts
+// over as well (its results overwrite the first pass's), except for the dense registers, whose
+// first-pass results are kept like their aggregates (dense_run is not repeated).
+void reset_family_store(dse_ctx* ctx, ObsFamily f, int n_t) {
+  std::vector<std::vector<double>>& store = ctx->fam[f].store;
+  store.resize(ctx->probs.size());
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
-    std::vector<double>& st = ctx->pair_store[pi];
-    const size_t want = pair_record(ctx, P) ? pair_store_size(P, n_t) : 0;
-    if (ctx->rerun && P.dn && pair_record(ctx, P) && st.size() == want) continue;
-    st.assign(want, 0.0);
+    const size_t want = obs_record(ctx, f, P) ? obs_store_size(f, P, n_t) : 0;
+    if (ctx->rerun && P.dn && store[pi].size() == want) continue;
+    store[pi].assign(want, 0.0);
   }
 }
 
-// the pair half of flush_partials: tiles in order, a loopback group's members into shard 0's record
-int flush_pair_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t) {
-  const size_t S = (size_t)ctx->pair_S;
+// the family's part of flush_partials: tiles in order, a loopback group's members into shard 0's record
+int flush_family_partials(dse_ctx* ctx, ObsFamily f, size_t nslots, size_t t0, int n_t) {
+  const ObsFamilyDesc& F = kObsFamilies[f];
+  ObsFamilyState& A = ctx->fam[f];
+  const size_t S = (size_t)A.S;
   std::vector<double> hs(nslots * ctx->total_items * S);
-  HIPC(hipMemcpy(hs.data(), ctx->d_pair_partial.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(hs.data(), A.d_partial.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
   std::vector<double> v(S);
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
-    if (P.side() || !pair_record(ctx, P)) continue;
+    if (P.side() || A.store[pi].empty()) continue;
     const size_t n_members = P.shard_bits > 0 ? (size_t(1) << P.shard_bits) : 1;
-    const int nv = 5 * (P.n * (P.n - 1) / 2);
+    const int nv = F.comps * F.units(P.n);
     for (size_t s = 0; s < nslots; ++s) {
       std::fill(v.begin(), v.end(), 0.0);
       for (size_t mi = pi; mi < pi + n_members; ++mi) {
@@ -1326,7 +1334,7 @@ int flush_pair_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t) {
         for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t)
           for (int j = 0; j <= nv; ++j) v[j] += row[t * S + j];
       }
-      finish_pairs(P.n, v.data(), ctx->pair_store[pi].data() + (t0 + s), (size_t)n_t);
+      finish_family(F, P.n, v.data(), A.store[pi].data() + (t0 + s), (size_t)n_t);
     }
   }
   return DSE_OK;
@@ -1378,30 +1386,9 @@ int flush_partials(dse_ctx* ctx, size_t nslots, size_t t0, int n_t, double* obs_
       }
     }
   }
-  if (ctx->pair_obs) {
-    const int prc = flush_pair_partials(ctx, nslots, t0, n_t);
-    if (prc) return prc;
-  }
-  if (!ctx->site_obs) return DSE_OK;
-  // the site sums of the same slots: tiles in order, a loopback group's members into shard 0's record
-  const size_t S = (size_t)ctx->site_S;
-  std::vector<double> hs(nslots * ctx->total_items * S);
-  HIPC(hipMemcpy(hs.data(), ctx->d_site_partial.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
-  std::vector<double> v(S);
-  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-    const HostProblem& P = ctx->probs[pi];
-    if (P.side() || ctx->site_store[pi].empty()) continue;
-    const size_t n_members = P.shard_bits > 0 ? (size_t(1) << P.shard_bits) : 1;
-    for (size_t s = 0; s < nslots; ++s) {
-      std::fill(v.begin(), v.end(), 0.0);
-      for (size_t mi = pi; mi < pi + n_members; ++mi) {
-        const double* row = hs.data() + (s * ctx->total_items + ctx->item_pos[mi]) * S;
-        for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t)
-          for (int j = 0; j <= 3 * P.n; ++j) v[j] += row[t * S + j];
-      }
-      finish_sites(P.n, v.data(), ctx->site_store[pi].data() + (t0 + s), (size_t)n_t);
-    }
-  }
+  for (ObsFamily f : kObsReadbackOrder)  // the family sums of the same slots
+    if (ctx->fam[f].on)
+      if (int rc = flush_family_partials(ctx, f, nslots, t0, n_t)) return rc;
   return DSE_OK;
 }
 
@@ -1559,12 +1546,9 @@ int dse_set_option(dse_ctx* ctx, const char* key, double value) {
     ctx->n_streams = (int)value;
     ctx->evolved = false;
     return ensure_lanes(ctx);
-  } else if (k == "site_obs") {  // site-resolved observables beside the seven aggregates
-    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "site_obs must be 0 or 1");
-    ctx->site_obs = (int)value;
-  } else if (k == "pair_obs") {  // two-spin correlators of every pair of register bits
-    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "pair_obs must be 0 or 1");
-    ctx->pair_obs = (int)value;
+  } else if (k == kObsFamilies[kSite].option || k == kObsFamilies[kPair].option) {  // beside the seven aggregates
+    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, k + " must be 0 or 1");
+    ctx->fam[k == kObsFamilies[kSite].option ? kSite : kPair].on = (int)value;
   } else if (k == "persistent") {
     ctx->persistent = value != 0.0;
   } else if (k == "swap_overlap") {
@@ -2060,16 +2044,14 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   }
   if (int rc = ctx->d_small.reserve(ctx, desc.size(), "small-engine allocation failed")) return rc;
   HIPC(hipMemcpy(ctx->d_small.p, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
-  if (ctx->site_obs) {
-    const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallSiteStride;
-    if (int rc = ctx->d_small_sites.reserve(ctx, sn, "small-engine site output allocation failed")) return rc;
+  double* d_fam[kNumObsFamilies] = {nullptr, nullptr};  // the enabled families' outputs
+  for (ObsFamily f : kObsLaunchOrder) {
+    if (!ctx->fam[f].on) continue;
+    const size_t sn = ctx->probs.size() * (size_t)n_t * kObsFamilies[f].small_stride;
+    const std::string what = std::string("small-engine ") + kObsFamilies[f].noun + " output allocation failed";
+    if (int rc = ctx->fam[f].d_small.reserve(ctx, sn, what.c_str())) return rc;
+    d_fam[f] = ctx->fam[f].d_small.p;
   }
-  double* const d_sites = ctx->site_obs ? ctx->d_small_sites.p : nullptr;
-  if (ctx->pair_obs) {
-    const size_t sn = ctx->probs.size() * (size_t)n_t * kSmallPairStride;
-    if (int rc = ctx->d_small_pairs.reserve(ctx, sn, "small-engine pair output allocation failed")) return rc;
-  }
-  double* const d_pairs = ctx->pair_obs ? ctx->d_small_pairs.p : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
   if (int rc = ctx->d_small_out.reserve(ctx, outn, "small-engine output allocation failed")) return rc;
   // selections per register size, then the interval -> set map
@@ -2087,13 +2069,13 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
-                           ctx->d_small_out.p, st, d_sites, d_pairs));
+                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_sites, d_pairs));
+                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
       *launches += 1.0;
     }
   }
@@ -2114,26 +2096,13 @@ int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
       finish_obs(P, h.data() + (pi * (size_t)n_t + ti) * 8, obs_out + pi * DSE_N_OBS * (size_t)n_t + ti,
                  (size_t)n_t);
   }
-  if (ctx->pair_obs) {
-    std::vector<double> hp(ctx->probs.size() * (size_t)n_t * kSmallPairStride);
-    HIPC(hipMemcpy(hp.data(), ctx->d_small_pairs.p, hp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-      const HostProblem& P = ctx->probs[pi];
-      if (!P.sm) continue;
-      for (int ti = 0; ti < n_t; ++ti)
-        finish_pairs(P.n, hp.data() + (pi * (size_t)n_t + ti) * kSmallPairStride, ctx->pair_store[pi].data() + ti,
-                     (size_t)n_t);
-    }
-  }
-  if (!ctx->site_obs) return DSE_OK;
-  std::vector<double> hs(ctx->probs.size() * (size_t)n_t * kSmallSiteStride);
-  HIPC(hipMemcpy(hs.data(), ctx->d_small_sites.p, hs.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-    const HostProblem& P = ctx->probs[pi];
-    if (!P.sm) continue;
-    for (int ti = 0; ti < n_t; ++ti)
-      finish_sites(P.n, hs.data() + (pi * (size_t)n_t + ti) * kSmallSiteStride, ctx->site_store[pi].data() + ti,
-                   (size_t)n_t);
+  for (ObsFamily f : kObsReadbackOrder) {
+    if (!ctx->fam[f].on) continue;
+    const size_t S = (size_t)kObsFamilies[f].small_stride;
+    std::vector<double> hf(ctx->probs.size() * (size_t)n_t * S);
+    HIPC(hipMemcpy(hf.data(), ctx->fam[f].d_small.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
+      if (ctx->probs[pi].sm) finish_family_outputs(ctx, f, pi, hf.data() + pi * (size_t)n_t * S, S, n_t);
   }
   return DSE_OK;
 }
@@ -2163,6 +2132,16 @@ constexpr size_t kEigHalfMinDim = 2048;
 // dropped (profiles/r04/eig_point_outputs_per_register.jsonl).
 constexpr size_t kEig2MinDim = 8192;
 
+// The dimensions from which option eig_impl sends a register to eig_sym_lower (half_min) and, of
+// those, to eig_sym_2stage (two_min); dsyevd below (SIZE_MAX: never)
+struct EigThresholds {
+  size_t half_min, two_min;
+};
+EigThresholds eig_thresholds(int eig_impl) {
+  return {eig_impl == 1 ? kEigHalfMinDim : (eig_impl == 2 || eig_impl == 3) ? (size_t)1024 : SIZE_MAX,
+          eig_impl == 1 ? kEig2MinDim : eig_impl == 3 ? (size_t)1024 : SIZE_MAX};
+}
+
 // Seconds of device time, by the measured rates: the Chebyshev propagator at ~15 TF/s of its
 // algorithmic FP64 work (the N = 14 bench runs at 16.5 chip-level) with ~25 extra terms per
 // output interval, against one eigendecomposition plus the Psi' GEMM at ~40 TF/s and the
@@ -2178,10 +2157,8 @@ bool dense_cheaper(const HostProblem& P, const double* t, int n_t, int eig_impl)
   const double alpha = 0.5 * (P.e_max - P.e_min);
   const double terms = alpha * (t[n_t - 1] - t[0]) + 25.0 * (n_t - 1);
   const double cheb = terms * dim * (P.flops_per_amp > 0 ? P.flops_per_amp : 300.0) / 15e12;
-  // the solver eig_impl takes for this size (dense_run's half_min / two_min)
   const size_t d = (size_t)dim;
-  const size_t half_min = eig_impl == 1 ? kEigHalfMinDim : (eig_impl == 2 || eig_impl == 3) ? 1024 : SIZE_MAX;
-  const size_t two_min = eig_impl == 1 ? kEig2MinDim : eig_impl == 3 ? 1024 : SIZE_MAX;
+  const auto [half_min, two_min] = eig_thresholds(eig_impl);  // the solver eig_impl takes for this size
   double eig = d >= half_min ? 0.047 + 2.96e-13 * dim * dim * dim + 3.73e-9 * dim * dim
                              : 1e-4 + 6.4e-13 * dim * dim * dim + 4.9e-9 * dim * dim + (dim >= 1024 ? 2e-2 : 0.0);
   if (d >= two_min && dim >= 16384.0) eig *= 0.61;  // two-stage: 1.43 vs 2.35 s at 2^14 (level at 2^13)
@@ -2213,432 +2190,540 @@ struct DevArena {  // device allocations of one dense_run, freed on every exit p
 // eig_streams solver streams at once (largest first, across sizes), then the output GEMMs.
 // Blocking; writes obs_out.
 
-struct DenseJob {
+struct DenseJob {  // registers of one size, built, solved and output together
   int n = 0, cnt = 0, TB = 1;
   size_t dim = 0, pstride = 0;
+  double per = 0.0;       // modelled device bytes per register
   std::vector<int> list;  // problem indices
   DevArena ba;
   double *V = nullptr, *lam = nullptr, *lam_lo = nullptr, *E = nullptr, *Pm = nullptr, *Psi = nullptr, *obs = nullptr;
   double* diag_dd = nullptr;
-  double* sites = nullptr;  // option site_obs: [cnt][n_t][site_stride(n)] raw site sums
-  double* pairs = nullptr;  // option pair_obs: [cnt][n_t][pair_stride(n)] raw pair sums
-  double* c = nullptr;      // custom psi(t0): [cnt][2 dim] projected coefficients (else not allocated)
+  double* fam[kNumObsFamilies] = {nullptr, nullptr};  // enabled families: [cnt][n_t][stride(n)] raw sums
+  double* c = nullptr;  // custom psi(t0): [cnt][2 dim] projected coefficients (else not allocated)
+  double* tabs = nullptr;
   rocblas_int* info = nullptr;
   DenseProb* d_desc = nullptr;
 };
 
-int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* ms_all, double* ms_eig) {
+// half-matrix eigensolver scratch of one solver stream: a copy of H' (the solver's A; V receives the
+// eigenvectors), tau and the tridiagonalisation workspace
+struct EigScratch {
+  double *A = nullptr, *tau = nullptr, *work = nullptr;
+};
+
+// What one dense_run holds across its rounds
+struct DenseRun {
+  const double* t = nullptr;  // dse_evolve's arguments
+  int n_t = 0;
+  double* obs_out = nullptr;
   std::vector<int> order;  // dense problems, by register size
-  {
-    std::map<int, std::vector<int>> by_n;
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
-      if (ctx->probs[pi].dn) by_n[ctx->probs[pi].n_local].push_back((int)pi);
-    for (auto& kv : by_n) order.insert(order.end(), kv.second.begin(), kv.second.end());
-  }
-  if (order.empty()) return DSE_OK;
-  const auto c0 = std::chrono::steady_clock::now();
-  double eig_ms = 0.0;
-  if (!ctx->dense_stream) HIPC(hipStreamCreateWithFlags(&ctx->dense_stream, hipStreamNonBlocking));
-  if (!ctx->blas && rocblas_create_handle(&ctx->blas) != rocblas_status_success)
-    return fail(ctx, DSE_ERR_HIP, "rocblas_create_handle failed");
-  hipStream_t st = ctx->dense_stream;
-  if (rocblas_set_stream(ctx->blas, st) != rocblas_status_success)
-    return fail(ctx, DSE_ERR_HIP, "rocblas_set_stream failed");
+  size_t idx = 0;          // the first of them not yet in a round
+  hipStream_t st = nullptr;  // dense_stream
   DevArena arena;
-  std::vector<double> tau(n_t);
-  for (int i = 0; i < n_t; ++i) tau[i] = t[i] - t[0];
-  double* d_tau = arena.get<double>(n_t);
-  if (!d_tau) return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed");
-  HIPC(hipMemcpyAsync(d_tau, tau.data(), n_t * sizeof(double), hipMemcpyHostToDevice, st));
+  std::vector<double> tau;  // t - t[0], and its device copy
+  double* d_tau = nullptr;
   // the non-uniform FFT's grid and device buffers (sized for the largest eligible register), or none
-  ctx->nufft_problems = 0;
   NufftGrid ngrid;
   NufftScratch nscr;
   DevArena nufft_arena;
   bool use_nufft = false;
-  if (ctx->dense_nufft && (ctx->dense_nufft == 2 || n_t >= kNufftMinOutputs)) {
-    size_t nmax = 0;
-    double lam_max = 0.0;
-    for (int pi : order) {
-      const HostProblem& P = ctx->probs[pi];
-      if ((size_t(1) << P.n_local) < (size_t)kNufftMinDim && ctx->dense_nufft != 2) continue;
-      nmax = std::max(nmax, size_t(1) << P.n_local);
-      lam_max = std::max({lam_max, std::fabs(P.e_min - P.shift), std::fabs(P.e_max - P.shift)});
-    }
-    if (nmax && nufft_grid(tau.data(), n_t, lam_max, ngrid)) {
-      nscr.U = nufft_arena.get<double2>((size_t)ngrid.M * nmax);
-      nscr.U2 = nufft_arena.get<double2>((size_t)ngrid.M * nmax);
-      nscr.c = nufft_arena.get<double>(nmax);
-      nscr.off = nufft_arena.get<int>((size_t)ngrid.M + 1);
-      nscr.nnz_cap = nmax * (size_t)(kNufftW + 2);
-      nscr.src = nufft_arena.get<int>(nscr.nnz_cap);
-      nscr.wt = nufft_arena.get<double>(4 * nscr.nnz_cap);
-      nscr.scale = nufft_arena.get<double>(n_t);
-      nscr.delta = nufft_arena.get<double>(n_t);
-      use_nufft = nscr.U && nscr.U2 && nscr.c && nscr.off && nscr.src && nscr.wt && nscr.scale && nscr.delta;
-      if (use_nufft) {
-        HIPC(hipMemcpyAsync(nscr.scale, ngrid.scale.data(), n_t * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPC(hipMemcpyAsync(nscr.delta, ngrid.delta.data(), n_t * sizeof(double), hipMemcpyHostToDevice, st));
-        HIPC(hipStreamSynchronize(st));
-      } else {  // no room: the GEMM outputs
-        (void)hipGetLastError();
-        nufft_arena.free_all();
-      }
-    }
-  }
-  double out_ms = 0.0;
-  struct EigScratch {
-    double *A = nullptr, *tau = nullptr, *work = nullptr;
-  };
+  // solver scratch per solver stream, sized for the largest such register so far; kept across rounds
   std::unique_ptr<DevArena> scr_arena;
   std::vector<EigScratch> scr;
   size_t scr_dim = 0, scr_work = 0;
-  size_t idx = 0;
-  while (idx < order.size()) {
-    // ---- round: jobs while 60% of the free memory lasts (at least one register) ----
+  double out_ms = 0.0, eig_ms = 0.0;
+};
+
+struct DenseTask {
+  DenseJob* j;
+  int i;  // register within the job; -1: the whole job, batched
+};
+
+// One round: the jobs that fit 60% of the free memory, their eigendecompositions as tasks over K
+// solver streams, and the queue between the workers and the output stage
+struct DenseRound {
+  std::vector<std::unique_ptr<DenseJob>> jobs;
+  std::vector<DenseTask> tasks;
+  int K = 1;
+  EigThresholds thr{SIZE_MAX, SIZE_MAX};  // eig_thresholds of the option; half_min SIZE_MAX without scratch
+  std::atomic<size_t> next{0};
+  std::atomic<bool> abort_all{false};
+  std::vector<rocblas_status> wst;  // per worker: the first failure
+  std::vector<int> wrc;
+  std::vector<hipError_t> werr;
+  std::mutex qm;
+  std::condition_variable qcv;
+  std::deque<DenseJob*> ready;       // jobs whose registers are all solved: their outputs next
+  std::map<DenseJob*, int> pending;  // per job: its registers not yet solved
+  int workers_left = 0;
+  std::chrono::steady_clock::time_point e0, e1;  // the solves: from the first task to the last worker's end
+};
+
+std::vector<int> dense_order(const dse_ctx* ctx) {  // the dense problems by register size, else by index
+  std::vector<int> order;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
+    if (ctx->probs[pi].dn) order.push_back((int)pi);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ctx->probs[a].n_local < ctx->probs[b].n_local; });
+  return order;
+}
+
+// dense_stream, the rocBLAS handle on it, and the output times on the device
+int dense_setup_stream(dse_ctx* ctx, DenseRun& R) {
+  if (!ctx->dense_stream) HIPC(hipStreamCreateWithFlags(&ctx->dense_stream, hipStreamNonBlocking));
+  if (!ctx->blas && rocblas_create_handle(&ctx->blas) != rocblas_status_success)
+    return fail(ctx, DSE_ERR_HIP, "rocblas_create_handle failed");
+  R.st = ctx->dense_stream;
+  if (rocblas_set_stream(ctx->blas, R.st) != rocblas_status_success)
+    return fail(ctx, DSE_ERR_HIP, "rocblas_set_stream failed");
+  R.tau.resize(R.n_t);
+  for (int i = 0; i < R.n_t; ++i) R.tau[i] = R.t[i] - R.t[0];
+  R.d_tau = R.arena.get<double>(R.n_t);
+  if (!R.d_tau) return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed");
+  HIPC(hipMemcpyAsync(R.d_tau, R.tau.data(), R.n_t * sizeof(double), hipMemcpyHostToDevice, R.st));
+  return DSE_OK;
+}
+
+// use_nufft with its grid and buffers when the option, the grid and the memory allow (else the GEMM outputs)
+int dense_setup_nufft(dse_ctx* ctx, DenseRun& R) {
+  const int n_t = R.n_t;
+  ctx->nufft_problems = 0;
+  if (!(ctx->dense_nufft && (ctx->dense_nufft == 2 || n_t >= kNufftMinOutputs))) return DSE_OK;
+  size_t nmax = 0;
+  double lam_max = 0.0;
+  for (int pi : R.order) {
+    const HostProblem& P = ctx->probs[pi];
+    if ((size_t(1) << P.n_local) < (size_t)kNufftMinDim && ctx->dense_nufft != 2) continue;
+    nmax = std::max(nmax, size_t(1) << P.n_local);
+    lam_max = std::max({lam_max, std::fabs(P.e_min - P.shift), std::fabs(P.e_max - P.shift)});
+  }
+  if (!nmax || !nufft_grid(R.tau.data(), n_t, lam_max, R.ngrid)) return DSE_OK;
+  NufftScratch& nscr = R.nscr;
+  nscr.U = R.nufft_arena.get<double2>((size_t)R.ngrid.M * nmax);
+  nscr.U2 = R.nufft_arena.get<double2>((size_t)R.ngrid.M * nmax);
+  nscr.c = R.nufft_arena.get<double>(nmax);
+  nscr.off = R.nufft_arena.get<int>((size_t)R.ngrid.M + 1);
+  nscr.nnz_cap = nmax * (size_t)(kNufftW + 2);
+  nscr.src = R.nufft_arena.get<int>(nscr.nnz_cap);
+  nscr.wt = R.nufft_arena.get<double>(4 * nscr.nnz_cap);
+  nscr.scale = R.nufft_arena.get<double>(n_t);
+  nscr.delta = R.nufft_arena.get<double>(n_t);
+  R.use_nufft = nscr.U && nscr.U2 && nscr.c && nscr.off && nscr.src && nscr.wt && nscr.scale && nscr.delta;
+  if (R.use_nufft) {
+    HIPC(hipMemcpyAsync(nscr.scale, R.ngrid.scale.data(), n_t * sizeof(double), hipMemcpyHostToDevice, R.st));
+    HIPC(hipMemcpyAsync(nscr.delta, R.ngrid.delta.data(), n_t * sizeof(double), hipMemcpyHostToDevice, R.st));
+    HIPC(hipStreamSynchronize(R.st));
+  } else {  // no room: the GEMM outputs
+    (void)hipGetLastError();
+    R.nufft_arena.free_all();
+  }
+  return DSE_OK;
+}
+
+// The next job: the registers of R.order[R.idx]'s size that fit `room` bytes (at least one when the
+// round is still empty), with its device buffers.  J stays null when the round is full: no room by the
+// model, or an allocation failed beside earlier jobs (the register waits for the next round).
+int dense_alloc_job(dse_ctx* ctx, const DenseRun& R, double room, bool round_empty, std::unique_ptr<DenseJob>& J) {
+  const int n = ctx->probs[R.order[R.idx]].n_local, n_t = R.n_t;
+  const size_t dim = size_t(1) << n;
+  // outputs per block: P and Psi' of a problem take 2 x dim x 2 TB doubles (<= 256 MiB each)
+  const int TB = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_t, (size_t(256) << 20) / (16 * dim)));
+  const size_t pstride = dim * 2 * (size_t)TB;
+  size_t fS[kNumObsFamilies] = {0, 0};  // the enabled families' sums per output
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on) fS[f] = (size_t)kObsFamilies[f].stride(n);
+  const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + fS[kSite] + fS[kPair]) + 2 * n * n + 4 * n) * sizeof(double));
+  size_t same = 0;
+  while (R.idx + same < R.order.size() && ctx->probs[R.order[R.idx + same]].n_local == n) ++same;
+  size_t cnt = (size_t)std::max(0.0, room / per);
+  if (cnt == 0 && !round_empty) return DSE_OK;
+  cnt = std::max<size_t>(1, std::min(cnt, same));
+  J = std::make_unique<DenseJob>();
+  J->n = n, J->dim = dim, J->TB = TB, J->pstride = pstride, J->cnt = (int)cnt, J->per = per;
+  J->list.assign(R.order.begin() + R.idx, R.order.begin() + R.idx + cnt);
+  DevArena& ba = J->ba;
+  J->V = ba.get<double>(dim * dim * cnt);
+  J->lam = ba.get<double>(dim * cnt);
+  J->lam_lo = ba.get<double>(dim * cnt);
+  J->diag_dd = ba.get<double>(2 * dim * cnt);
+  J->E = ba.get<double>(dim * cnt);
+  J->info = ba.get<rocblas_int>(cnt);
+  J->Pm = ba.get<double>(pstride * cnt);
+  J->Psi = ba.get<double>(pstride * cnt);
+  J->obs = ba.get<double>((size_t)n_t * 8 * cnt);
+  for (ObsFamily f : kObsLaunchOrder)
+    if (fS[f]) J->fam[f] = ba.get<double>((size_t)n_t * fS[f] * cnt);
+  bool any_custom = false;
+  for (size_t i = 0; i < cnt; ++i) any_custom = any_custom || ctx->probs[J->list[i]].init_kind != 0;
+  bool ok = !any_custom || (J->c = ba.get<double>(2 * dim * cnt));
+  if (ok) {
+    J->tabs = ba.get<double>((size_t)(2 * n * n + 5 * n) * cnt);
+    J->d_desc = ba.get<DenseProb>(cnt);
+  }
+  ok = ok && J->V && J->lam && J->lam_lo && J->diag_dd && J->E && J->info && J->Pm && J->Psi && J->obs && J->tabs &&
+       J->d_desc && !(fS[kSite] && !J->fam[kSite]) && !(fS[kPair] && !J->fam[kPair]);
+  if (ok) return DSE_OK;
+  J.reset();
+  if (!round_empty) return DSE_OK;
+  return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
+}
+
+
+// The job's tables and descriptors on the device, and H' of its registers in V
+int dense_fill_job(dse_ctx* ctx, const DenseRun& R, DenseJob& J) {
+  const int n = J.n, n_t = R.n_t;
+  const size_t dim = J.dim, cnt = (size_t)J.cnt, tsz = (size_t)(2 * n * n + 5 * n);
+  std::vector<double> htabs(tsz * cnt, 0.0);
+  std::vector<DenseProb> desc(cnt);
+  for (size_t i = 0; i < cnt; ++i) {
+    const HostProblem& P = ctx->probs[J.list[i]];
+    double* h = htabs.data() + tsz * i;
+    std::copy(P.field.begin(), P.field.begin() + n, h);
+    std::copy(P.zz.begin(), P.zz.begin() + n * n, h + n);
+    std::copy(P.pair.begin(), P.pair.begin() + n * n, h + n + n * n);
+    std::copy(P.flip.begin(), P.flip.begin() + 4 * n, h + n + 2 * n * n);
+    double* d = J.tabs + tsz * i;
+    DenseProb& D = desc[i];
+    D.n = n;
+    D.rot = P.imag ? 1 : 0;
+    D.sea_mask = P.sea_mask;
+    D.rare_bit = P.rare_bit;
+    D.n_sea = __builtin_popcountll(P.sea_mask);
+    D.x0 = P.init_kind ? 0 : P.psi0;  // custom psi(t0): the whole phase i^|x| is in phi0
+    if (P.init_kind) {             // (buf[0] holds psi(t0) until k_dense_final overwrites it)
+      D.init = P.buf[0];
+      D.c = J.c + 2 * dim * i;
+    }
+    D.shift = P.shift;
+    D.field = d;
+    D.zz = d + n;
+    D.pair = d + n + n * n;
+    D.flip = d + n + 2 * n * n;
+    D.V = J.V + dim * dim * i;
+    D.lam = J.lam + dim * i;
+    D.lam_lo = J.lam_lo + dim * i;
+    D.diag_dd = J.diag_dd + 2 * dim * i;
+    D.refine = ctx->dense_refine;
+    D.obs = J.obs + (size_t)n_t * 8 * i;
+    D.final_state = P.buf[0];
+    for (ObsFamily f : kObsLaunchOrder)
+      D.*kObsFamilies[f].dense_out = J.fam[f] ? J.fam[f] + (size_t)n_t * kObsFamilies[f].stride(n) * i : nullptr;
+  }
+  hipStream_t st = R.st;
+  HIPC(hipMemcpyAsync(J.tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPC(hipMemcpyAsync(J.d_desc, desc.data(), desc.size() * sizeof(DenseProb), hipMemcpyHostToDevice, st));
+  HIPC(hipMemsetAsync(J.V, 0, dim * dim * cnt * sizeof(double), st));
+  HIPC(launch_dense_h(J.d_desc, (int)cnt, (int)dim, st));
+  HIPC(hipStreamSynchronize(st));  // the host tables may go
+  return DSE_OK;
+}
+
+// The round's eigendecompositions: one task per large register, one batched task per job of small
+// ones, largest first
+void dense_list_tasks(DenseRound& Rd) {
+  for (auto& J : Rd.jobs) {
+    if (J->dim >= 1024)
+      for (int i = 0; i < J->cnt; ++i) Rd.tasks.push_back({J.get(), i});
+    else
+      Rd.tasks.push_back({J.get(), -1});
+  }
+  std::stable_sort(Rd.tasks.begin(), Rd.tasks.end(),
+                   [](const DenseTask& x, const DenseTask& y) { return x.j->dim > y.j->dim; });
+  for (const DenseTask& T : Rd.tasks) Rd.pending[T.j] += 1;
+}
+
+// K solver streams, each with a rocBLAS handle (kept in the context)
+int dense_ensure_solver_streams(dse_ctx* ctx, int K) {
+  while ((int)ctx->eig_h.size() < K) {
+    hipStream_t es = nullptr;
+    rocblas_handle eh = nullptr;
+    HIPC(hipStreamCreateWithFlags(&es, hipStreamNonBlocking));
+    if (rocblas_create_handle(&eh) != rocblas_status_success || rocblas_set_stream(eh, es) != rocblas_status_success) {
+      if (eh) (void)rocblas_destroy_handle(eh);
+      (void)hipStreamDestroy(es);
+      return fail(ctx, DSE_ERR_HIP, "rocblas handle for the eigensolver streams failed");
+    }
+    ctx->eig_st.push_back(es);
+    ctx->eig_h.push_back(eh);
+  }
+  return DSE_OK;
+}
+
+// The half-matrix and two-stage solvers' scratch per solver stream, sized for the round's largest such
+// register.  Without room beside the round's jobs the round solves with dsyevd in place (half_min).
+void dense_ensure_scratch(DenseRun& R, DenseRound& Rd) {
+  size_t half_dim = 0, two_dim = 0;
+  for (const DenseTask& T : Rd.tasks)
+    if (T.i >= 0 && T.j->dim >= Rd.thr.half_min) {
+      half_dim = std::max(half_dim, T.j->dim);
+      if (T.j->dim >= Rd.thr.two_min) two_dim = std::max(two_dim, T.j->dim);
+    }
+  const size_t work_b = std::max(sytrd_workspace((int)half_dim), two_dim ? eig2_workspace((int)two_dim) : (size_t)0);
+  if (half_dim <= R.scr_dim && work_b <= R.scr_work) return;
+  R.scr.clear();
+  R.scr_arena.reset(new DevArena);
+  R.scr_dim = 0, R.scr_work = 0;
+  for (int w = 0; w < Rd.K; ++w) {
+    EigScratch S;
+    S.A = R.scr_arena->get<double>(half_dim * half_dim);
+    S.tau = R.scr_arena->get<double>(half_dim);
+    S.work = R.scr_arena->get<double>(work_b / sizeof(double) + 1);
+    if (!S.A || !S.tau || !S.work) break;
+    R.scr.push_back(S);
+  }
+  if ((int)R.scr.size() == Rd.K) {
+    R.scr_dim = half_dim, R.scr_work = work_b;
+  } else {
+    (void)hipGetLastError();
+    R.scr.clear();
+    R.scr_arena.reset();
+    Rd.thr.half_min = SIZE_MAX;
+  }
+}
+
+// Task T on solver stream w, to the end of its stream's work: the two-stage, the half-matrix or
+// rocSOLVER's solver by the register's size (the batched dsyevd for a whole job of small ones).
+// False: a failure, left in werr / wst / wrc[w].
+bool dense_solve_task(dse_ctx* ctx, const DenseRun& R, DenseRound& Rd, int w, const DenseTask& T) {
+  DenseJob& J = *T.j;
+  hipStream_t es = ctx->eig_st[w];
+  rocblas_handle eh = ctx->eig_h[w];
+  hipError_t& err = Rd.werr[w];
+  rocblas_status& rst = Rd.wst[w];
+  int& rc = Rd.wrc[w];
+  const rocblas_int dim = (rocblas_int)J.dim;
+  if (T.i >= 0 && J.dim >= Rd.thr.half_min) {
+    const size_t i = (size_t)T.i;
+    const EigScratch& S = R.scr[w];
+    double* Vi = J.V + J.dim * J.dim * i;
+    err = hipMemcpyAsync(S.A, Vi, J.dim * J.dim * sizeof(double), hipMemcpyDeviceToDevice, es);
+    if (err == hipSuccess && J.dim >= Rd.thr.two_min) {
+      rc = eig_sym_2stage(eh, es, dim, S.A, dim, J.lam + J.dim * i, Vi, dim, J.E + J.dim * i, S.work, J.info + i,
+                          ctx->n_cu, ctx->eig_spin);
+      if (rc == kEig2PollTimeout) {  // a poll gave up (workgroups not co-resident): H' again, dsyevd
+        ctx->eig_fallbacks++;
+        rc = 0;
+        err = hipMemsetAsync(Vi, 0, J.dim * J.dim * sizeof(double), es);
+        if (err == hipSuccess) err = launch_dense_h(J.d_desc + i, 1, (int)J.dim, es);
+        if (err == hipSuccess)
+          rst = rocsolver_dsyevd(eh, rocblas_evect_original, rocblas_fill_upper, dim, Vi, dim, J.lam + J.dim * i,
+                                 J.E + J.dim * i, J.info + i);
+      }
+    } else if (err == hipSuccess) {
+      rc = eig_sym_lower(eh, es, dim, S.A, dim, J.lam + J.dim * i, Vi, dim, J.E + J.dim * i, S.tau, S.work, J.info + i);
+    }
+  } else if (T.i >= 0) {
+    const size_t i = (size_t)T.i;
+    rst = rocsolver_dsyevd(eh, rocblas_evect_original, rocblas_fill_upper, dim, J.V + J.dim * J.dim * i, dim,
+                           J.lam + J.dim * i, J.E + J.dim * i, J.info + i);
+  } else {
+    rst = rocsolver_dsyevd_strided_batched(eh, rocblas_evect_original, rocblas_fill_upper, dim, J.V, dim,
+                                           (rocblas_stride)(J.dim * J.dim), J.lam, (rocblas_stride)J.dim, J.E,
+                                           (rocblas_stride)J.dim, J.info, J.cnt);
+  }
+  const hipError_t se = hipStreamSynchronize(es);
+  if (err == hipSuccess) err = se;
+  return err == hipSuccess && rst == rocblas_status_success && rc == 0;
+}
+
+// Solver worker w: tasks largest first; a job whose last register is solved goes to the output queue
+void dense_worker(dse_ctx* ctx, const DenseRun& R, DenseRound& Rd, int w) {
+  for (size_t ti = Rd.next++; ti < Rd.tasks.size() && !Rd.abort_all; ti = Rd.next++) {
+    const DenseTask& T = Rd.tasks[ti];
+    if (!dense_solve_task(ctx, R, Rd, w, T)) {
+      Rd.abort_all = true;
+      break;
+    }
+    std::lock_guard<std::mutex> lk(Rd.qm);
+    if (--Rd.pending[T.j] == 0) {
+      Rd.ready.push_back(T.j);
+      Rd.qcv.notify_one();
+    }
+  }
+  std::lock_guard<std::mutex> lk(Rd.qm);
+  if (--Rd.workers_left == 0) Rd.e1 = std::chrono::steady_clock::now();
+  Rd.qcv.notify_one();
+}
+
+// Job J's outputs by the non-uniform FFT: per register, Psi' interleaved, the observables per block
+int dense_outputs_nufft(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
+  const int n_t = R.n_t;
+  const size_t dim = J.dim;
+  hipStream_t st = R.st;
+  for (int i = 0; i < J.cnt; ++i) {
+    const DenseProb* di = J.d_desc + i;
+    auto per_block = [&](int tb0, int tb) -> int {
+      if (launch_dense_obs_c(di, (int)dim, J.Psi, tb, tb0, st) != hipSuccess) return -1;
+      for (ObsFamily f : kObsLaunchOrder)
+        if (J.fam[f] && kObsFamilies[f].launch_dense_c(di, (int)dim, J.Psi, tb, tb0, kObsFamilies[f].stride(J.n), st) != hipSuccess)
+          return -1;
+      if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, J.Psi, tb, R.tau[n_t - 1], st) != hipSuccess)
+        return -1;
+      return 0;
+    };
+    const HostProblem& P = ctx->probs[J.list[i]];
+    // the low parts exist only after k_dense_rq: without the refinement none are passed (zero)
+    const double* lo = ctx->dense_refine ? J.lam_lo + dim * i : nullptr;
+    const int rc = nufft_outputs(ctx->nufft, st, R.ngrid, R.nscr, J.V + dim * dim * i, J.lam + dim * i, lo, P.psi0,
+                                 (int)dim, J.Psi, J.TB, per_block, P.init_kind ? J.c + 2 * dim * i : nullptr);
+    if (rc) return fail(ctx, DSE_ERR_HIP, "dense engine: non-uniform FFT outputs failed (" + std::to_string(rc) + ")");
+    ctx->nufft_problems++;
+  }
+  return DSE_OK;
+}
+
+// Job J's outputs in blocks of TB times: Psi' = V [cos | -sin] for all its registers at once
+int dense_outputs_gemm(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
+  const int n_t = R.n_t, cnt = J.cnt;
+  const size_t dim = J.dim, pstride = J.pstride;
+  const DenseProb* desc = J.d_desc;
+  hipStream_t st = R.st;
+  const double one = 1.0, zero = 0.0;
+  for (int tb0 = 0; tb0 < n_t; tb0 += J.TB) {
+    const int tb = std::min(J.TB, n_t - tb0);
+    HIPC(launch_dense_phase(desc, cnt, (int)dim, R.d_tau + tb0, tb, J.Pm, pstride, st));
+    if (J.c) HIPC(launch_dense_phase_c(desc, cnt, (int)dim, R.d_tau + tb0, tb, J.Pm, pstride, st));
+    const rocblas_status rs = rocblas_dgemm_strided_batched(
+        ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)dim, 2 * tb, (rocblas_int)dim, &one,
+        J.V, (rocblas_int)dim, (rocblas_stride)(dim * dim), J.Pm, (rocblas_int)dim, (rocblas_stride)pstride, &zero,
+        J.Psi, (rocblas_int)dim, (rocblas_stride)pstride, cnt);
+    if (rs != rocblas_status_success)
+      return fail(ctx, DSE_ERR_HIP, "rocblas dgemm failed (status " + std::to_string((int)rs) + ")");
+    HIPC(launch_dense_obs(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, st));
+    for (ObsFamily f : kObsLaunchOrder)
+      if (J.fam[f])
+        HIPC(kObsFamilies[f].launch_dense(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, kObsFamilies[f].stride(J.n), st));
+    if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, J.Psi, pstride, tb, R.tau[n_t - 1], st));
+  }
+  return DSE_OK;
+}
+
+// Job J's sums back on the host and normalised: the families into their stores, the aggregates into
+// obs_out.  out_ms: the output stage since o0, up to the families' results.
+int dense_read_back(dse_ctx* ctx, DenseRun& R, DenseJob& J, std::chrono::steady_clock::time_point o0) {
+  const int n_t = R.n_t, cnt = J.cnt;
+  hipStream_t st = R.st;
+  std::vector<double> h((size_t)n_t * 8 * cnt);
+  HIPC(hipMemcpyAsync(h.data(), J.obs, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  std::vector<double> hf[kNumObsFamilies];
+  for (ObsFamily f : kObsLaunchOrder) {
+    if (!J.fam[f]) continue;
+    hf[f].resize((size_t)n_t * kObsFamilies[f].stride(J.n) * cnt);
+    HIPC(hipMemcpyAsync(hf[f].data(), J.fam[f], hf[f].size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIPC(hipStreamSynchronize(st));
+  for (ObsFamily f : kObsReadbackOrder) {
+    const size_t S = (size_t)kObsFamilies[f].stride(J.n);
+    for (int i = 0; i < cnt && J.fam[f]; ++i)
+      finish_family_outputs(ctx, f, (size_t)J.list[i], hf[f].data() + (size_t)i * n_t * S, S, n_t);
+  }
+  R.out_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - o0).count();
+  for (int i = 0; i < cnt; ++i) {
+    const int pi = J.list[i];
+    for (int ti = 0; ti < n_t; ++ti)
+      finish_obs(ctx->probs[pi], h.data() + ((size_t)i * n_t + ti) * 8, R.obs_out + (size_t)pi * DSE_N_OBS * n_t + ti,
+                 (size_t)n_t);
+  }
+  return DSE_OK;
+}
+
+// The output stage of job J, every register of it: Psi' by the transform or the GEMM, observables and
+// the final state from Psi', on dense_stream
+int dense_outputs(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
+  hipStream_t st = R.st;
+  std::vector<rocblas_int> hinfo(J.cnt);
+  HIPC(hipMemcpyAsync(hinfo.data(), J.info, J.cnt * sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  for (int i = 0; i < J.cnt; ++i)
+    if (hinfo[i] != 0)
+      return fail(ctx, DSE_ERR_CONVERGENCE, "dense engine: eigensolver did not converge (info " +
+                                                std::to_string(hinfo[i]) + ")");
+  const auto o0 = std::chrono::steady_clock::now();
+  if (ctx->dense_refine) HIPC(launch_dense_rq(J.d_desc, J.cnt, (int)J.dim, st));
+  if (J.c) HIPC(launch_dense_project(J.d_desc, J.cnt, (int)J.dim, st));  // c = V^T phi0 of the custom states
+  const bool nufft = R.use_nufft && (J.dim >= (size_t)kNufftMinDim || ctx->dense_nufft == 2);
+  if (int rc = nufft ? dense_outputs_nufft(ctx, R, J) : dense_outputs_gemm(ctx, R, J)) return rc;
+  return dense_read_back(ctx, R, J, o0);
+}
+
+// One round's solves and outputs: K workers take the tasks, and this thread runs the output stage of
+// each job as its last register is solved (dense_stream) while the other solves go on (outputs per
+// register as each solve ends measured the same, profiles/r05/fullsweep_outputs_ab.jsonl)
+int dense_run_round(dse_ctx* ctx, DenseRun& R, DenseRound& Rd) {
+  const int K = Rd.K;
+  Rd.wst.assign(K, rocblas_status_success);
+  Rd.wrc.assign(K, 0);
+  Rd.werr.assign(K, hipSuccess);
+  Rd.workers_left = K;
+  Rd.e1 = Rd.e0;
+  std::vector<std::thread> th;
+  for (int w = 0; w < K; ++w) th.emplace_back(dense_worker, ctx, std::cref(R), std::ref(Rd), w);
+  int orc = DSE_OK;
+  size_t done = 0;
+  const size_t n_out_tasks = Rd.jobs.size();
+  while (done < n_out_tasks) {
+    DenseJob* J = nullptr;
+    {
+      std::unique_lock<std::mutex> lk(Rd.qm);
+      Rd.qcv.wait(lk, [&] { return !Rd.ready.empty() || Rd.workers_left == 0; });
+      if (Rd.ready.empty()) break;  // the workers stopped early: an error below
+      J = Rd.ready.front();
+      Rd.ready.pop_front();
+    }
+    orc = dense_outputs(ctx, R, *J);
+    if (orc != DSE_OK) {
+      Rd.abort_all = true;
+      break;
+    }
+    ++done;
+  }
+  for (auto& x : th) x.join();
+  if (orc != DSE_OK) return orc;
+  for (int w = 0; w < K; ++w) {
+    if (Rd.werr[w] != hipSuccess)
+      return fail(ctx, DSE_ERR_HIP, std::string("eigensolver stream: ") + hipGetErrorString(Rd.werr[w]));
+    if (Rd.wst[w] != rocblas_status_success)
+      return fail(ctx, DSE_ERR_HIP, "rocsolver dsyevd failed (status " + std::to_string((int)Rd.wst[w]) + ")");
+    if (Rd.wrc[w] != 0)
+      return fail(ctx, DSE_ERR_HIP, "half-matrix eigensolver failed (step " + std::to_string(-Rd.wrc[w]) + ")");
+  }
+  if (done < n_out_tasks) return fail(ctx, DSE_ERR_HIP, "dense engine: eigensolver workers stopped early");
+  R.eig_ms += std::chrono::duration<double, std::milli>(Rd.e1 - Rd.e0).count();
+  return DSE_OK;
+}
+
+int dense_run(dse_ctx* ctx, const double* t, int n_t, double* obs_out, double* ms_all, double* ms_eig) {
+  DenseRun R;
+  R.t = t, R.n_t = n_t, R.obs_out = obs_out;
+  R.order = dense_order(ctx);
+  if (R.order.empty()) return DSE_OK;
+  const auto c0 = std::chrono::steady_clock::now();
+  int rc;
+  if ((rc = dense_setup_stream(ctx, R)) || (rc = dense_setup_nufft(ctx, R))) return rc;
+  while (R.idx < R.order.size()) {
+    DenseRound Rd;  // jobs while 60% of the free memory lasts (at least one register)
     size_t free_b = 0, total_b = 0;
     HIPC(hipMemGetInfo(&free_b, &total_b));
     const double budget = 0.6 * (double)free_b;
-    double used = 0.0;
-    std::vector<std::unique_ptr<DenseJob>> jobs;
-    while (idx < order.size()) {
-      const int n = ctx->probs[order[idx]].n_local;
-      const size_t dim = size_t(1) << n;
-      // outputs per block: P and Psi' of a problem take 2 x dim x 2 TB doubles (<= 256 MiB each)
-      const int TB = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_t, (size_t(256) << 20) / (16 * dim)));
-      const size_t pstride = dim * 2 * (size_t)TB;
-      const size_t sS = ctx->site_obs ? (size_t)site_stride(n) : 0;  // site sums per output
-      const size_t pS = ctx->pair_obs ? (size_t)pair_stride(n) : 0;  // pair sums per output
-      const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + sS + pS) + 2 * n * n + 4 * n) * sizeof(double));
-      size_t same = 0;
-      while (idx + same < order.size() && ctx->probs[order[idx + same]].n_local == n) ++same;
-      size_t cnt = (size_t)std::max(0.0, (budget - used) / per);
-      if (cnt == 0 && !jobs.empty()) break;
-      cnt = std::max<size_t>(1, std::min(cnt, same));
-      auto J = std::make_unique<DenseJob>();
-      J->n = n, J->dim = dim, J->TB = TB, J->pstride = pstride, J->cnt = (int)cnt;
-      J->list.assign(order.begin() + idx, order.begin() + idx + cnt);
-      DevArena& ba = J->ba;
-      J->V = ba.get<double>(dim * dim * cnt);
-      J->lam = ba.get<double>(dim * cnt);
-      J->lam_lo = ba.get<double>(dim * cnt);
-      J->diag_dd = ba.get<double>(2 * dim * cnt);
-      J->E = ba.get<double>(dim * cnt);
-      J->info = ba.get<rocblas_int>(cnt);
-      J->Pm = ba.get<double>(pstride * cnt);
-      J->Psi = ba.get<double>(pstride * cnt);
-      J->obs = ba.get<double>((size_t)n_t * 8 * cnt);
-      J->sites = sS ? ba.get<double>((size_t)n_t * sS * cnt) : nullptr;
-      J->pairs = pS ? ba.get<double>((size_t)n_t * pS * cnt) : nullptr;
-      bool any_custom = false;
-      for (size_t i = 0; i < cnt; ++i) any_custom = any_custom || ctx->probs[J->list[i]].init_kind != 0;
-      if (any_custom && !(J->c = ba.get<double>(2 * dim * cnt))) {
-        if (!jobs.empty()) break;
-        return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
-      }
-      const size_t tsz = (size_t)(2 * n * n + 5 * n);
-      double* tabs = ba.get<double>(tsz * cnt);
-      J->d_desc = ba.get<DenseProb>(cnt);
-      if (!J->V || !J->lam || !J->lam_lo || !J->diag_dd || !J->E || !J->info || !J->Pm || !J->Psi || !J->obs || !tabs || !J->d_desc ||
-          (sS && !J->sites) || (pS && !J->pairs)) {
-        if (!jobs.empty()) break;  // this round is full: the register waits for the next one
-        return fail(ctx, DSE_ERR_OOM, "dense engine: allocation failed (dim " + std::to_string(dim) + ")");
-      }
-      std::vector<double> htabs(tsz * cnt, 0.0);
-      std::vector<DenseProb> desc(cnt);
-      for (size_t i = 0; i < cnt; ++i) {
-        const HostProblem& P = ctx->probs[J->list[i]];
-        double* h = htabs.data() + tsz * i;
-        std::copy(P.field.begin(), P.field.begin() + n, h);
-        std::copy(P.zz.begin(), P.zz.begin() + n * n, h + n);
-        std::copy(P.pair.begin(), P.pair.begin() + n * n, h + n + n * n);
-        std::copy(P.flip.begin(), P.flip.begin() + 4 * n, h + n + 2 * n * n);
-        double* d = tabs + tsz * i;
-        DenseProb& D = desc[i];
-        D.n = n;
-        D.rot = P.imag ? 1 : 0;
-        D.sea_mask = P.sea_mask;
-        D.rare_bit = P.rare_bit;
-        D.n_sea = __builtin_popcountll(P.sea_mask);
-        D.x0 = P.init_kind ? 0 : P.psi0;  // custom psi(t0): the whole phase i^|x| is in phi0
-        if (P.init_kind) {             // (buf[0] holds psi(t0) until k_dense_final overwrites it)
-          D.init = P.buf[0];
-          D.c = J->c + 2 * dim * i;
-        }
-        D.shift = P.shift;
-        D.field = d;
-        D.zz = d + n;
-        D.pair = d + n + n * n;
-        D.flip = d + n + 2 * n * n;
-        D.V = J->V + dim * dim * i;
-        D.lam = J->lam + dim * i;
-        D.lam_lo = J->lam_lo + dim * i;
-        D.diag_dd = J->diag_dd + 2 * dim * i;
-        D.refine = ctx->dense_refine;
-        D.obs = J->obs + (size_t)n_t * 8 * i;
-        D.final_state = P.buf[0];
-        D.sites = sS ? J->sites + (size_t)n_t * sS * i : nullptr;
-        D.pairs = pS ? J->pairs + (size_t)n_t * pS * i : nullptr;
-      }
-      HIPC(hipMemcpyAsync(tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
-      HIPC(hipMemcpyAsync(J->d_desc, desc.data(), desc.size() * sizeof(DenseProb), hipMemcpyHostToDevice, st));
-      HIPC(hipMemsetAsync(J->V, 0, dim * dim * cnt * sizeof(double), st));
-      HIPC(launch_dense_h(J->d_desc, (int)cnt, (int)dim, st));
-      HIPC(hipStreamSynchronize(st));  // the host tables may go
-      used += per * (double)cnt;
-      idx += cnt;
-      jobs.push_back(std::move(J));
+    for (double used = 0.0; R.idx < R.order.size();) {
+      std::unique_ptr<DenseJob> J;
+      if ((rc = dense_alloc_job(ctx, R, budget - used, Rd.jobs.empty(), J))) return rc;
+      if (!J) break;
+      if ((rc = dense_fill_job(ctx, R, *J))) return rc;
+      used += J->per * (double)J->cnt;
+      R.idx += (size_t)J->cnt;
+      Rd.jobs.push_back(std::move(J));
     }
-    // ---- the round's eigendecompositions: one task per large register, one batched task per job of
-    // small ones, largest first, over up to eig_streams solver streams ----
-    const auto e0 = std::chrono::steady_clock::now();
-    struct Task {
-      DenseJob* j;
-      int i;  // register within the job; -1: the whole job, batched
-    };
-    std::vector<Task> tasks;
-    for (auto& J : jobs) {
-      if (J->dim >= 1024)
-        for (int i = 0; i < J->cnt; ++i) tasks.push_back({J.get(), i});
-      else
-        tasks.push_back({J.get(), -1});
-    }
-    std::stable_sort(tasks.begin(), tasks.end(), [](const Task& x, const Task& y) { return x.j->dim > y.j->dim; });
-    const int K = std::max(1, std::min(ctx->eig_streams, (int)tasks.size()));
-    while ((int)ctx->eig_h.size() < K) {
-      hipStream_t es = nullptr;
-      rocblas_handle eh = nullptr;
-      HIPC(hipStreamCreateWithFlags(&es, hipStreamNonBlocking));
-      if (rocblas_create_handle(&eh) != rocblas_status_success || rocblas_set_stream(eh, es) != rocblas_status_success) {
-        if (eh) (void)rocblas_destroy_handle(eh);
-        (void)hipStreamDestroy(es);
-        return fail(ctx, DSE_ERR_HIP, "rocblas handle for the eigensolver streams failed");
-      }
-      ctx->eig_st.push_back(es);
-      ctx->eig_h.push_back(eh);
-    }
-    // half-matrix eigensolver scratch per solver stream: a copy of H' (the solver's A; V receives
-    // the eigenvectors), tau and the tridiagonalisation workspace, sized for the round's largest
-    // such register; kept across rounds
-    size_t half_min = ctx->eig_impl == 2 ? 1024 : ctx->eig_impl == 1 ? kEigHalfMinDim : ctx->eig_impl == 3 ? 1024 : SIZE_MAX;
-    const size_t two_min = ctx->eig_impl == 3 ? 1024 : ctx->eig_impl == 1 ? kEig2MinDim : SIZE_MAX;
-    size_t half_dim = 0, two_dim = 0;
-    for (const Task& T : tasks)
-      if (T.i >= 0 && T.j->dim >= half_min) {
-        half_dim = std::max(half_dim, T.j->dim);
-        if (T.j->dim >= two_min) two_dim = std::max(two_dim, T.j->dim);
-      }
-    const size_t work_b = std::max(sytrd_workspace((int)half_dim), two_dim ? eig2_workspace((int)two_dim) : (size_t)0);
-    if (half_dim > scr_dim || work_b > scr_work) {
-      scr.clear();
-      scr_arena.reset(new DevArena);
-      scr_dim = 0, scr_work = 0;
-      for (int w = 0; w < K; ++w) {
-        EigScratch S;
-        S.A = scr_arena->get<double>(half_dim * half_dim);
-        S.tau = scr_arena->get<double>(half_dim);
-        S.work = scr_arena->get<double>(work_b / sizeof(double) + 1);
-        if (!S.A || !S.tau || !S.work) break;
-        scr.push_back(S);
-      }
-      if ((int)scr.size() == K) {
-        scr_dim = half_dim, scr_work = work_b;
-      } else {  // no room beside the round's jobs: dsyevd in place
-        (void)hipGetLastError();
-        scr.clear();
-        scr_arena.reset();
-        half_min = SIZE_MAX;
-      }
-    }
-    // the workers take tasks largest first; a job whose last register is solved goes to the output
-    // queue, and this thread runs its output GEMMs (dense_stream) while the other solves go on
-    // (outputs per register as each solve ends measured the same: 3.51-3.56 s per N = 14 point
-    // either way over 16 points, profiles/r05/fullsweep_outputs_ab.jsonl)
-    std::atomic<size_t> next{0};
-    std::atomic<bool> abort_all{false};
-    std::vector<rocblas_status> wst(K, rocblas_status_success);
-    std::vector<int> wrc(K, 0);
-    std::vector<hipError_t> werr(K, hipSuccess);
-    std::mutex qm;
-    std::condition_variable qcv;
-    std::deque<DenseJob*> ready;        // jobs whose registers are all solved: their outputs next
-    std::map<DenseJob*, int> pending;  // per job: its registers not yet solved
-    for (const Task& T : tasks) pending[T.j] += 1;
-    int workers_left = K;
-    auto e1 = e0;
-    auto worker = [&](int w) {
-      for (size_t ti = next++; ti < tasks.size() && !abort_all; ti = next++) {
-        const Task& T = tasks[ti];
-        DenseJob& J = *T.j;
-        const rocblas_int dim = (rocblas_int)J.dim;
-        if (T.i >= 0 && J.dim >= half_min) {
-          const size_t i = (size_t)T.i;
-          double* Vi = J.V + J.dim * J.dim * i;
-          werr[w] = hipMemcpyAsync(scr[w].A, Vi, J.dim * J.dim * sizeof(double), hipMemcpyDeviceToDevice,
-                                   ctx->eig_st[w]);
-          if (werr[w] == hipSuccess && J.dim >= two_min) {
-            wrc[w] = eig_sym_2stage(ctx->eig_h[w], ctx->eig_st[w], dim, scr[w].A, dim, J.lam + J.dim * i, Vi, dim,
-                                    J.E + J.dim * i, scr[w].work, J.info + i, ctx->n_cu, ctx->eig_spin);
-            if (wrc[w] == kEig2PollTimeout) {  // a poll gave up (workgroups not co-resident): H' again, dsyevd
-              ctx->eig_fallbacks++;
-              wrc[w] = 0;
-              werr[w] = hipMemsetAsync(Vi, 0, J.dim * J.dim * sizeof(double), ctx->eig_st[w]);
-              if (werr[w] == hipSuccess) werr[w] = launch_dense_h(J.d_desc + i, 1, (int)J.dim, ctx->eig_st[w]);
-              if (werr[w] == hipSuccess)
-                wst[w] = rocsolver_dsyevd(ctx->eig_h[w], rocblas_evect_original, rocblas_fill_upper, dim, Vi, dim,
-                                          J.lam + J.dim * i, J.E + J.dim * i, J.info + i);
-            }
-          }
-          else if (werr[w] == hipSuccess)
-            wrc[w] = eig_sym_lower(ctx->eig_h[w], ctx->eig_st[w], dim, scr[w].A, dim, J.lam + J.dim * i, Vi, dim,
-                                   J.E + J.dim * i, scr[w].tau, scr[w].work, J.info + i);
-        } else if (T.i >= 0) {
-          const size_t i = (size_t)T.i;
-          wst[w] = rocsolver_dsyevd(ctx->eig_h[w], rocblas_evect_original, rocblas_fill_upper, dim,
-                                    J.V + J.dim * J.dim * i, dim, J.lam + J.dim * i, J.E + J.dim * i, J.info + i);
-        } else {
-          wst[w] = rocsolver_dsyevd_strided_batched(ctx->eig_h[w], rocblas_evect_original, rocblas_fill_upper, dim,
-                                                    J.V, dim, (rocblas_stride)(J.dim * J.dim), J.lam,
-                                                    (rocblas_stride)J.dim, J.E, (rocblas_stride)J.dim, J.info, J.cnt);
-        }
-        const hipError_t se = hipStreamSynchronize(ctx->eig_st[w]);
-        if (werr[w] == hipSuccess) werr[w] = se;
-        if (werr[w] != hipSuccess || wst[w] != rocblas_status_success || wrc[w] != 0) {
-          abort_all = true;
-          break;
-        }
-        std::lock_guard<std::mutex> lk(qm);
-        if (--pending[&J] == 0) {
-          ready.push_back(&J);
-          qcv.notify_one();
-        }
-      }
-      std::lock_guard<std::mutex> lk(qm);
-      if (--workers_left == 0) e1 = std::chrono::steady_clock::now();
-      qcv.notify_one();
-    };
-    auto outputs = [&](DenseJob& J) -> int {  // every register of job J
-      const int i0 = 0, cnt = J.cnt, TB = J.TB;
-      const size_t dim = J.dim, pstride = J.pstride;
-      const DenseProb* desc = J.d_desc + i0;
-      double* const V = J.V + dim * dim * i0;
-      double* const Pm = J.Pm + pstride * i0;
-      double* const Psi = J.Psi + pstride * i0;
-      std::vector<rocblas_int> hinfo(cnt);
-      HIPC(hipMemcpyAsync(hinfo.data(), J.info + i0, cnt * sizeof(rocblas_int), hipMemcpyDeviceToHost, st));
-      HIPC(hipStreamSynchronize(st));
-      for (int i = 0; i < cnt; ++i)
-        if (hinfo[i] != 0)
-          return fail(ctx, DSE_ERR_CONVERGENCE, "dense engine: eigensolver did not converge (info " +
-                                                    std::to_string(hinfo[i]) + ")");
-      const double one = 1.0, zero = 0.0;
-      const auto o0 = std::chrono::steady_clock::now();
-      if (ctx->dense_refine) HIPC(launch_dense_rq(desc, cnt, (int)dim, st));
-      if (J.c) HIPC(launch_dense_project(desc, cnt, (int)dim, st));  // c = V^T phi0 of the custom states
-      if (use_nufft && (dim >= (size_t)kNufftMinDim || ctx->dense_nufft == 2)) {  // per register, Psi' interleaved
-        for (int i = 0; i < cnt; ++i) {
-          const DenseProb* di = desc + i;
-          auto per_block = [&](int tb0, int tb) -> int {
-            if (launch_dense_obs_c(di, (int)dim, Psi, tb, tb0, st) != hipSuccess) return -1;
-            if (J.sites && launch_dense_obs_sites_c(di, (int)dim, Psi, tb, tb0, site_stride(J.n), st) != hipSuccess)
-              return -1;
-            if (J.pairs && launch_dense_obs_pairs_c(di, (int)dim, Psi, tb, tb0, pair_stride(J.n), st) != hipSuccess)
-              return -1;
-            if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, Psi, tb, tau[n_t - 1], st) != hipSuccess)
-              return -1;
-            return 0;
-          };
-          // the low parts exist only after k_dense_rq: without the refinement none are passed (zero)
-          const double* lo = ctx->dense_refine ? J.lam_lo + dim * (i0 + i) : nullptr;
-          const int rc = nufft_outputs(ctx->nufft, st, ngrid, nscr, V + dim * dim * i, J.lam + dim * (i0 + i), lo,
-                                       ctx->probs[J.list[i0 + i]].psi0, (int)dim, Psi, TB, per_block,
-                                       ctx->probs[J.list[i0 + i]].init_kind ? J.c + 2 * dim * (i0 + i) : nullptr);
-          if (rc) return fail(ctx, DSE_ERR_HIP, "dense engine: non-uniform FFT outputs failed (" + std::to_string(rc) + ")");
-          ctx->nufft_problems++;
-        }
-      } else
-      for (int tb0 = 0; tb0 < n_t; tb0 += TB) {
-        const int tb = std::min(TB, n_t - tb0);
-        HIPC(launch_dense_phase(desc, cnt, (int)dim, d_tau + tb0, tb, Pm, pstride, st));
-        if (J.c) HIPC(launch_dense_phase_c(desc, cnt, (int)dim, d_tau + tb0, tb, Pm, pstride, st));
-        const rocblas_status rs = rocblas_dgemm_strided_batched(
-            ctx->blas, rocblas_operation_none, rocblas_operation_none, (rocblas_int)dim, 2 * tb, (rocblas_int)dim, &one,
-            V, (rocblas_int)dim, (rocblas_stride)(dim * dim), Pm, (rocblas_int)dim, (rocblas_stride)pstride, &zero,
-            Psi, (rocblas_int)dim, (rocblas_stride)pstride, cnt);
-        if (rs != rocblas_status_success)
-          return fail(ctx, DSE_ERR_HIP, "rocblas dgemm failed (status " + std::to_string((int)rs) + ")");
-        HIPC(launch_dense_obs(desc, cnt, (int)dim, Psi, pstride, tb, tb0, st));
-        if (J.sites) HIPC(launch_dense_obs_sites(desc, cnt, (int)dim, Psi, pstride, tb, tb0, site_stride(J.n), st));
-        if (J.pairs) HIPC(launch_dense_obs_pairs(desc, cnt, (int)dim, Psi, pstride, tb, tb0, pair_stride(J.n), st));
-        if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, Psi, pstride, tb, tau[n_t - 1], st));
-      }
-      std::vector<double> h((size_t)n_t * 8 * cnt);
-      HIPC(hipMemcpyAsync(h.data(), J.obs + (size_t)n_t * 8 * i0, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      std::vector<double> hs;
-      if (J.sites) {
-        hs.resize((size_t)n_t * site_stride(J.n) * cnt);
-        HIPC(hipMemcpyAsync(hs.data(), J.sites, hs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
-      std::vector<double> hpr;
-      if (J.pairs) {
-        hpr.resize((size_t)n_t * pair_stride(J.n) * cnt);
-        HIPC(hipMemcpyAsync(hpr.data(), J.pairs, hpr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-      }
-      HIPC(hipStreamSynchronize(st));
-      for (int i = 0; i < cnt && J.pairs; ++i)
-        for (int ti = 0; ti < n_t; ++ti)
-          finish_pairs(J.n, hpr.data() + ((size_t)i * n_t + ti) * pair_stride(J.n),
-                       ctx->pair_store[J.list[i]].data() + ti, (size_t)n_t);
-      for (int i = 0; i < cnt && J.sites; ++i)
-        for (int ti = 0; ti < n_t; ++ti)
-          finish_sites(J.n, hs.data() + ((size_t)i * n_t + ti) * site_stride(J.n),
-                       ctx->site_store[J.list[i]].data() + ti, (size_t)n_t);
-      out_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - o0).count();
-      for (int i = 0; i < cnt; ++i) {
-        const int pi = J.list[i0 + i];
-        for (int ti = 0; ti < n_t; ++ti)
-          finish_obs(ctx->probs[pi], h.data() + ((size_t)i * n_t + ti) * 8,
-                     obs_out + (size_t)pi * DSE_N_OBS * n_t + ti, (size_t)n_t);
-      }
-      return DSE_OK;
-    };
-    std::vector<std::thread> th;
-    for (int w = 0; w < K; ++w) th.emplace_back(worker, w);
-    int orc = DSE_OK;
-    size_t done = 0;
-    const size_t n_out_tasks = jobs.size();
-    while (done < n_out_tasks) {
-      DenseJob* J = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(qm);
-        qcv.wait(lk, [&] { return !ready.empty() || workers_left == 0; });
-        if (ready.empty()) break;  // the workers stopped early: an error below
-        J = ready.front();
-        ready.pop_front();
-      }
-      orc = outputs(*J);
-      if (orc != DSE_OK) {
-        abort_all = true;
-        break;
-      }
-      ++done;
-    }
-    for (auto& x : th) x.join();
-    if (orc != DSE_OK) return orc;
-    for (int w = 0; w < K; ++w) {
-      if (werr[w] != hipSuccess)
-        return fail(ctx, DSE_ERR_HIP, std::string("eigensolver stream: ") + hipGetErrorString(werr[w]));
-      if (wst[w] != rocblas_status_success)
-        return fail(ctx, DSE_ERR_HIP, "rocsolver dsyevd failed (status " + std::to_string((int)wst[w]) + ")");
-      if (wrc[w] != 0)
-        return fail(ctx, DSE_ERR_HIP, "half-matrix eigensolver failed (step " + std::to_string(-wrc[w]) + ")");
-    }
-    if (done < n_out_tasks) return fail(ctx, DSE_ERR_HIP, "dense engine: eigensolver workers stopped early");
-    eig_ms += std::chrono::duration<double, std::milli>(e1 - e0).count();
+    Rd.e0 = std::chrono::steady_clock::now();
+    dense_list_tasks(Rd);
+    Rd.K = std::max(1, std::min(ctx->eig_streams, (int)Rd.tasks.size()));
+    if ((rc = dense_ensure_solver_streams(ctx, Rd.K))) return rc;
+    Rd.thr = eig_thresholds(ctx->eig_impl);
+    dense_ensure_scratch(R, Rd);
+    if ((rc = dense_run_round(ctx, R, Rd))) return rc;
   }
   if (ms_all) *ms_all = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-  if (ms_eig) *ms_eig = eig_ms;
-  ctx->dense_out_ms = out_ms;
+  if (ms_eig) *ms_eig = R.eig_ms;
+  ctx->dense_out_ms = R.out_ms;
   return DSE_OK;
 }
 
@@ -2739,12 +2824,11 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
                oDesc = take(sizeof(DenseProb)), oProb = take(sizeof(DevProb)),
                oCoef = take(std::max(row.size() * sizeof(double2), cf.size() * sizeof(double))), oErr = take(sizeof(int)),
                oCnt = take(nb * sizeof(int));
-  // option site_obs: the site sums of the same states, kept with the mode's other buffers (taken
-  // last and only with the option on: every other offset, and the size with it off, as before)
-  const int sS = site_stride(n);
-  const size_t oSites = ctx->site_obs ? take((size_t)n_t * sS * sizeof(double)) : 0;
-  const int pS = pair_stride(n);  // option pair_obs: likewise
-  const size_t oPairs = ctx->pair_obs ? take((size_t)n_t * pS * sizeof(double)) : 0;
+  // the enabled observable families: their sums of the same states, kept with the mode's other buffers
+  // (taken last and only with the option on: every other offset, and the size with it off, as before)
+  size_t oFam[kNumObsFamilies] = {0, 0};
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on) oFam[f] = take((size_t)n_t * kObsFamilies[f].stride(n) * sizeof(double));
   if (int rc = ctx->d_mx.reserve(ctx, off, "propagator-matrix mode: allocation failed")) return rc;
   unsigned char* base = ctx->d_mx.p;
   double2* U = reinterpret_cast<double2*>(base + oU);     // tiles (real build) or columns: U e_c
@@ -2853,21 +2937,17 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.n_sea = __builtin_popcountll(P.sea_mask);
   D.x0 = P.psi0;
   D.obs = d_obs;
-  if (ctx->site_obs) D.sites = reinterpret_cast<double*>(base + oSites);
-  if (ctx->pair_obs) D.pairs = reinterpret_cast<double*>(base + oPairs);
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on) D.*kObsFamilies[f].dense_out = reinterpret_cast<double*>(base + oFam[f]);
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
-  std::vector<double> hsites;
-  if (D.sites) {
-    hsites.resize((size_t)n_t * sS);
-    HIPC(launch_dense_obs_sites_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, sS, st));
-    HIPC(hipMemcpyAsync(hsites.data(), D.sites, hsites.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  std::vector<double> hpairs;
-  if (D.pairs) {
-    hpairs.resize((size_t)n_t * pS);
-    HIPC(launch_dense_obs_pairs_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, pS, st));
-    HIPC(hipMemcpyAsync(hpairs.data(), D.pairs, hpairs.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  std::vector<double> hfam[kNumObsFamilies];
+  for (ObsFamily f : kObsLaunchOrder) {
+    if (!ctx->fam[f].on) continue;
+    const ObsFamilyDesc& F = kObsFamilies[f];
+    hfam[f].resize((size_t)n_t * F.stride(n));
+    HIPC(F.launch_dense_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, F.stride(n), st));
+    HIPC(hipMemcpyAsync(hfam[f].data(), D.*F.dense_out, hfam[f].size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPC(hipMemcpyAsync(P.buf[0], S + dim * (size_t)(n_t - 1), dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
   std::vector<double> h((size_t)n_t * 8);
@@ -2878,10 +2958,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   if (herr) return fail(ctx, DSE_ERR_HIP, "propagator-matrix mode: column build failed");
   for (int ti = 0; ti < n_t; ++ti)
     finish_obs(P, h.data() + (size_t)ti * 8, obs_out + (size_t)pi * DSE_N_OBS * n_t + ti, (size_t)n_t);
-  for (int ti = 0; ti < n_t && D.sites; ++ti)
-    finish_sites(n, hsites.data() + (size_t)ti * sS, ctx->site_store[pi].data() + ti, (size_t)n_t);
-  for (int ti = 0; ti < n_t && D.pairs; ++ti)
-    finish_pairs(n, hpairs.data() + (size_t)ti * pS, ctx->pair_store[pi].data() + ti, (size_t)n_t);
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on) finish_family_outputs(ctx, f, (size_t)pi, hfam[f].data(), (size_t)kObsFamilies[f].stride(n), n_t);
   P.degree = deg;
   *h_apps = (double)deg * (double)dim;
   float b_ms = 0.f, p_ms = 0.f;
@@ -2891,6 +2969,79 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   ctx->mx_products_ms = p_ms;
   ctx->mx_products = (double)std::max(0, n_t - 1 - j_first);
   ctx->mx_bytes_per_product = (double)(u_elems * sizeof(double2) + dim * sizeof(double2));
+  return DSE_OK;
+}
+
+// ---- hooks on a given state -------------------------------------------------------------------
+
+// the hook's state `in` (the members' parts consecutive) into role 0 of members first .. first + count - 1
+int upload_member_states(dse_ctx* ctx, int first, int count, const double2* in, hipStream_t st) {
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    const size_t amps = size_t(1) << P.n_local;
+    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
+  }
+  return DSE_OK;
+}
+
+int64_t member_tiles(const dse_ctx* ctx, int first, int count) {
+  int64_t tiles = 0;
+  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
+  return tiles;
+}
+
+// dse_site_observables / dse_pair_observables: family f of the state psi of register `problem`
+int obs_family_hook(dse_ctx* ctx, ObsFamily f, int problem, const double* psi, double* out) {
+  const ObsFamilyDesc& F = kObsFamilies[f];
+  if (!ctx) return DSE_ERR_ARG;
+  if (!psi || !out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  if (F.hook_refuses_shard_early && ctx->probs[first].dist)
+    return fail(ctx, DSE_ERR_ARG, std::string(F.hook) + ": not available for a dist shard");
+  HIPC(hipSetDevice(ctx->device));
+  if ((rc = prepare(ctx))) return rc;
+  if (!F.hook_refuses_shard_early && (rc = obs_family_refusal(ctx, f, F.hook))) return rc;
+  const int64_t tiles = member_tiles(ctx, first, count);
+  if ((rc = ensure_family_partial(ctx, f, 1))) return rc;
+  const size_t S = (size_t)ctx->fam[f].S;
+  double* const d_partial = ctx->fam[f].d_partial.p;
+  hipStream_t st = ctx->lanes[0].stream;
+  if ((rc = upload_member_states(ctx, first, count, reinterpret_cast<const double2*>(psi), st))) return rc;
+  int64_t off = 0;
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    HIPC(F.launch(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, d_partial + off * S, (int)S, st, 1, 0, 0));
+    off += P.n_tiles;
+  }
+  std::vector<double> h(tiles * S);
+  HIPC(hipMemcpyAsync(h.data(), d_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  const int n = ctx->probs[first].n;
+  const int nv = F.comps * F.units(n);
+  std::vector<double> v(S, 0.0);
+  for (int64_t t = 0; t < tiles; ++t)
+    for (int j = 0; j <= nv; ++j) v[j] += h[t * S + j];
+  finish_family(F, n, v.data(), out, 1);
+  ctx->evolved = false;
+  return DSE_OK;
+}
+
+// dse_get_site_obs / dse_get_pair_obs: register `problem`'s record of the last evolve (a register
+// without one, a non-zero shard, holds an empty store: its size differs)
+int obs_family_get(dse_ctx* ctx, ObsFamily f, int problem, double* out) {
+  if (!ctx) return DSE_ERR_ARG;
+  if (!out) return fail(ctx, DSE_ERR_ARG, "null pointer");
+  int first = 0, count = 1;
+  int rc = hook_members(ctx, problem, &first, &count);
+  if (rc) return rc;
+  const ObsFamilyState& A = ctx->fam[f];
+  if (A.nt <= 0 || (size_t)problem >= A.store.size() || (kObsFamilies[f].get_needs_option && !A.on) ||
+      A.store[problem].size() != obs_store_size(f, ctx->probs[problem], A.nt))
+    return fail(ctx, DSE_ERR_STATE, std::string("no ") + kObsFamilies[f].noun + " observables (set option " +
+                                        kObsFamilies[f].option + " = 1 and call dse_evolve first)");
+  std::copy(A.store[problem].begin(), A.store[problem].end(), out);
   return DSE_OK;
 }
 
@@ -2907,13 +3058,8 @@ int dse_apply_h(dse_ctx* ctx, int problem, const double* psi_in, double* psi_out
   HIPC(hipSetDevice(ctx->device));
   if ((rc = prepare(ctx))) return rc;
   hipStream_t st = ctx->lanes[0].stream;
-  const double2* in = reinterpret_cast<const double2*>(psi_in);
   double2* out = reinterpret_cast<double2*>(psi_out);
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    const size_t amps = size_t(1) << P.n_local;
-    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
-  }
+  if ((rc = upload_member_states(ctx, first, count, reinterpret_cast<const double2*>(psi_in), st))) return rc;
   if ((rc = apply_members(ctx, first, count, st))) return rc;
   for (int i = 0; i < count; ++i) {
     HostProblem& P = ctx->probs[first + i];
@@ -2933,16 +3079,10 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7) 
   if (rc) return rc;
   HIPC(hipSetDevice(ctx->device));
   if ((rc = prepare(ctx))) return rc;
-  int64_t tiles = 0;
-  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
+  const int64_t tiles = member_tiles(ctx, first, count);
   if ((rc = ensure_partial(ctx, 1))) return rc;
   hipStream_t st = ctx->lanes[0].stream;
-  const double2* in = reinterpret_cast<const double2*>(psi);
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    const size_t amps = size_t(1) << P.n_local;
-    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
-  }
+  if ((rc = upload_member_states(ctx, first, count, reinterpret_cast<const double2*>(psi), st))) return rc;
   if (ctx->probs[first].dist && (rc = dist_exchange(ctx, 0, 0, st))) return rc;
   int64_t off = 0;
   for (int i = 0; i < count; ++i) {
@@ -2962,117 +3102,14 @@ int dse_observables(dse_ctx* ctx, int problem, const double* psi, double* obs7) 
   return DSE_OK;
 }
 
-int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out) {
-  if (!ctx) return DSE_ERR_ARG;
-  if (!psi || !out) return fail(ctx, DSE_ERR_ARG, "null pointer");
-  int first = 0, count = 1;
-  int rc = hook_members(ctx, problem, &first, &count);
-  if (rc) return rc;
-  if (ctx->probs[first].dist)
-    return fail(ctx, DSE_ERR_ARG, "dse_site_observables: not available for a dist shard");
-  HIPC(hipSetDevice(ctx->device));
-  if ((rc = prepare(ctx))) return rc;
-  int64_t tiles = 0;
-  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
-  if ((rc = ensure_site_partial(ctx, 1))) return rc;
-  const size_t S = (size_t)ctx->site_S;
-  hipStream_t st = ctx->lanes[0].stream;
-  const double2* in = reinterpret_cast<const double2*>(psi);
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    const size_t amps = size_t(1) << P.n_local;
-    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
-  }
-  int64_t off = 0;
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    HIPC(launch_obs_sites(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_site_partial.p + off * S,
-                          (int)S, st));
-    off += P.n_tiles;
-  }
-  std::vector<double> h(tiles * S);
-  HIPC(hipMemcpyAsync(h.data(), ctx->d_site_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPC(hipStreamSynchronize(st));
-  const int n = ctx->probs[first].n;
-  std::vector<double> v(S, 0.0);
-  for (int64_t t = 0; t < tiles; ++t)
-    for (int j = 0; j <= 3 * n; ++j) v[j] += h[t * S + j];
-  finish_sites(n, v.data(), out, 1);
-  ctx->evolved = false;
-  return DSE_OK;
-}
+int dse_site_observables(dse_ctx* ctx, int problem, const double* psi, double* out) { return obs_family_hook(ctx, kSite, problem, psi, out); }
+int dse_site_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kSite].nt : DSE_ERR_ARG; }
+int dse_get_site_obs(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kSite, problem, out); }
 
-int dse_site_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->site_nt : DSE_ERR_ARG; }
-
-int dse_get_site_obs(dse_ctx* ctx, int problem, double* out) {
-  if (!ctx) return DSE_ERR_ARG;
-  if (!out) return fail(ctx, DSE_ERR_ARG, "null pointer");
-  int first = 0, count = 1;
-  int rc = hook_members(ctx, problem, &first, &count);
-  if (rc) return rc;
-  if (ctx->site_nt <= 0 || (size_t)problem >= ctx->site_store.size() ||
-      ctx->site_store[problem].size() != (size_t)3 * ctx->probs[problem].n * ctx->site_nt)
-    return fail(ctx, DSE_ERR_STATE, "no site observables (set option site_obs = 1 and call dse_evolve first)");
-  std::copy(ctx->site_store[problem].begin(), ctx->site_store[problem].end(), out);
-  return DSE_OK;
-}
-
-int dse_pair_observables(dse_ctx* ctx, int problem, const double* psi, double* out) {
-  if (!ctx) return DSE_ERR_ARG;
-  if (!psi || !out) return fail(ctx, DSE_ERR_ARG, "null pointer");
-  int first = 0, count = 1;
-  int rc = hook_members(ctx, problem, &first, &count);
-  if (rc) return rc;
-  HIPC(hipSetDevice(ctx->device));
-  if ((rc = prepare(ctx))) return rc;
-  if ((rc = pair_refusal(ctx, "dse_pair_observables"))) return rc;
-  int64_t tiles = 0;
-  for (int i = 0; i < count; ++i) tiles += ctx->probs[first + i].n_tiles;
-  if ((rc = ensure_pair_partial(ctx, 1))) return rc;
-  const size_t S = (size_t)ctx->pair_S;
-  hipStream_t st = ctx->lanes[0].stream;
-  const double2* in = reinterpret_cast<const double2*>(psi);
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    const size_t amps = size_t(1) << P.n_local;
-    HIPC(hipMemcpyAsync(P.buf[0], in + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice, st));
-  }
-  int64_t off = 0;
-  for (int i = 0; i < count; ++i) {
-    HostProblem& P = ctx->probs[first + i];
-    HIPC(launch_obs_pairs(P.L, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, ctx->d_pair_partial.p + off * S,
-                          (int)S, st));
-    off += P.n_tiles;
-  }
-  std::vector<double> h(tiles * S);
-  HIPC(hipMemcpyAsync(h.data(), ctx->d_pair_partial.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  HIPC(hipStreamSynchronize(st));
-  const int n = ctx->probs[first].n;
-  const int nv = 5 * (n * (n - 1) / 2);
-  std::vector<double> v(S, 0.0);
-  for (int64_t t = 0; t < tiles; ++t)
-    for (int j = 0; j <= nv; ++j) v[j] += h[t * S + j];
-  finish_pairs(n, v.data(), out, 1);
-  ctx->evolved = false;
-  return DSE_OK;
-}
-
-int dse_pair_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->pair_nt : DSE_ERR_ARG; }
-
-int dse_pair_obs_problems(const dse_ctx* ctx) { return ctx ? (ctx->pair_nt > 0 ? ctx->pair_problems : 0) : DSE_ERR_ARG; }
-
-int dse_get_pair_obs(dse_ctx* ctx, int problem, double* out) {
-  if (!ctx) return DSE_ERR_ARG;
-  if (!out) return fail(ctx, DSE_ERR_ARG, "null pointer");
-  int first = 0, count = 1;
-  int rc = hook_members(ctx, problem, &first, &count);
-  if (rc) return rc;
-  if (ctx->pair_nt <= 0 || (size_t)problem >= ctx->pair_store.size() || !pair_record(ctx, ctx->probs[problem]) ||
-      ctx->pair_store[problem].size() != pair_store_size(ctx->probs[problem], ctx->pair_nt))
-    return fail(ctx, DSE_ERR_STATE, "no pair observables (set option pair_obs = 1 and call dse_evolve first)");
-  std::copy(ctx->pair_store[problem].begin(), ctx->pair_store[problem].end(), out);
-  return DSE_OK;
-}
+int dse_pair_observables(dse_ctx* ctx, int problem, const double* psi, double* out) { return obs_family_hook(ctx, kPair, problem, psi, out); }
+int dse_pair_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kPair].nt : DSE_ERR_ARG; }
+int dse_pair_obs_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kPair) : DSE_ERR_ARG; }
+int dse_get_pair_obs(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kPair, problem, out); }
 
 int dse_has_feature(const char* name) {
   if (!name) return 0;
@@ -3369,14 +3406,9 @@ int choose_engines(dse_ctx* ctx, EvolvePlan& pl) {
     }
   }
   for (auto& P : ctx->probs) pl.any_big = pl.any_big || !P.side();
-  if (ctx->site_obs)
-    for (auto& P : ctx->probs)
-      if (P.dist)
-        return fail(ctx, DSE_ERR_ARG, "site_obs: not available for a register partitioned over processes "
-                                      "(the all-reduce of the site sums is not implemented)");
-  if (ctx->pair_obs && (rc = pair_refusal(ctx, "pair_obs"))) return rc;
-  reset_site_store(ctx, pl.n_t);
-  reset_pair_store(ctx, pl.n_t);
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on && (rc = obs_family_refusal(ctx, f, kObsFamilies[f].option))) return rc;
+  for (ObsFamily f : kObsLaunchOrder) reset_family_store(ctx, f, pl.n_t);
   pl.persistent = ctx->persistent != 0;
   return DSE_OK;
 }
@@ -4090,17 +4122,17 @@ int run_side_engines(dse_ctx* ctx, EvolvePlan& pl) {
 }
 
 // output slots per flush: what every arena in use holds under kPartialCapBytes (for the pair
-// arena one slot fits the cap: pair_refusal); the arenas; the timing events
+// arena one slot fits the cap: obs_family_refusal); the arenas; the timing events
 int size_obs_chunks(dse_ctx* ctx, EvolvePlan& pl) {
   const int64_t tiles = ctx->total_items;
   const int n_max = widest_register(ctx);
   int rc;
   pl.chunk = partial_chunk(tiles * 64, pl.M, pl.n_t);
-  if (ctx->site_obs) pl.chunk = std::min(pl.chunk, partial_chunk(tiles * site_stride(n_max) * 8, pl.M, pl.n_t));
-  if (ctx->pair_obs)
-    pl.chunk = std::min(pl.chunk, partial_chunk(std::max<int64_t>(1, tiles) * pair_stride(n_max) * 8, pl.M, pl.n_t));
-  if (ctx->site_obs && (rc = ensure_site_partial(ctx, pl.chunk))) return rc;
-  if (ctx->pair_obs && (rc = ensure_pair_partial(ctx, pl.chunk))) return rc;
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on)
+      pl.chunk = std::min(pl.chunk, partial_chunk(tiles * kObsFamilies[f].stride(n_max) * 8, pl.M, pl.n_t));
+  for (ObsFamily f : kObsLaunchOrder)
+    if (ctx->fam[f].on && (rc = ensure_family_partial(ctx, f, pl.chunk))) return rc;
   if ((rc = ensure_partial(ctx, pl.chunk))) return rc;
   if (ctx->time_every > 0)
     for (auto& ln : ctx->lanes) {
@@ -4123,12 +4155,12 @@ int launch_group_obs(dse_ctx* ctx, const LaneGroup& g, int bsel, size_t slot, in
   const size_t at = slot * ctx->total_items + g.off, stride = out_stride_slots * (size_t)ctx->total_items;
   HIPC(launch_obs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel, ctx->d_partial.p + at * 8, st, n_out,
                   stride * 8, xq));
-  if (ctx->site_obs)
-    HIPC(launch_obs_sites(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel,
-                          ctx->d_site_partial.p + at * ctx->site_S, ctx->site_S, st, n_out, stride * ctx->site_S, xq));
-  if (ctx->pair_obs)
-    HIPC(launch_obs_pairs(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel,
-                          ctx->d_pair_partial.p + at * ctx->pair_S, ctx->pair_S, st, n_out, stride * ctx->pair_S, xq));
+  for (ObsFamily f : kObsLaunchOrder) {
+    const ObsFamilyState& A = ctx->fam[f];
+    if (A.on)
+      HIPC(kObsFamilies[f].launch(g.L, ctx->d_probs, ctx->d_items + g.off, (int)g.count, bsel, A.d_partial.p + at * A.S,
+                                  A.S, st, n_out, stride * A.S, xq));
+  }
   return DSE_OK;
 }
 
@@ -4328,11 +4360,12 @@ int finish_evolve(dse_ctx* ctx, EvolvePlan& pl) {
   ctx->last_q = (int)pl.groups.size() & 1;
   for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
   ctx->evolved = true;
-  if (ctx->site_obs) ctx->site_nt = pl.n_t;  // the store is complete: dse_get_site_obs may read it
-  if (ctx->pair_obs) {
-    ctx->pair_nt = pl.n_t;
-    ctx->pair_problems = 0;
-    for (const auto& P : ctx->probs) ctx->pair_problems += pair_record(ctx, P) ? 1 : 0;
+  for (ObsFamily f : kObsLaunchOrder) {
+    ObsFamilyState& A = ctx->fam[f];
+    if (!A.on) continue;
+    A.nt = pl.n_t;  // the store is complete: the getter may read it
+    A.problems = 0;
+    for (const auto& P : ctx->probs) A.problems += obs_record(ctx, f, P) ? 1 : 0;
   }
   return DSE_OK;
 }
@@ -4350,8 +4383,6 @@ int fill_stats(dse_ctx* ctx, const EvolvePlan& pl, dse_stats* stats) {
     n_custom += (P.init_kind && (P.dist || P.shard_rank == 0)) ? 1 : 0;
     if (P.sm || P.mx) max_deg = std::max(max_deg, P.degree);
   }
-  int n_site = 0;
-  for (const auto& st : ctx->site_store) n_site += st.empty() ? 0 : 1;
   std::memset(stats, 0, sizeof(*stats));
   stats->h_applications = happl;
   stats->amplitude_updates = pl.amp_updates;
@@ -4367,7 +4398,7 @@ int fill_stats(dse_ctx* ctx, const EvolvePlan& pl, dse_stats* stats) {
   stats->dense_ms = pl.dense_ms;
   stats->dense_eig_ms = pl.dense_eig_ms;
   stats->dense_nufft_problems = pl.any_dense ? ctx->nufft_problems : 0;
-  stats->site_obs_problems = n_site;
+  stats->site_obs_problems = obs_family_problems(ctx, kSite);
   stats->dense_output_ms = pl.any_dense ? ctx->dense_out_ms : 0.0;
   stats->custom_init_problems = n_custom;
   stats->step_kernel_ms = tm.launches > 0 ? tm.step_ms : -1.0;
@@ -4441,11 +4472,10 @@ int dse_evolve(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_o
   if (!ctx) return DSE_ERR_ARG;
   ctx->handoff_fallbacks = 0;
   ctx->eig_fallbacks = 0;
-  // the site observables of an earlier evolve end here, whatever becomes of this call (an argument
-  // error before any work, a failure half way): dse_get_site_obs is DSE_ERR_STATE until an evolve
-  // with the option on has succeeded
-  ctx->site_nt = 0;
-  ctx->pair_nt = 0;  // (the pair observables likewise)
+  // the site and pair observables of an earlier evolve end here, whatever becomes of this call (an
+  // argument error before any work, a failure half way): their getters are DSE_ERR_STATE until an
+  // evolve with the option on has succeeded
+  for (auto& A : ctx->fam) A.nt = 0;
   ctx->final_valid = false;
   int rc = evolve_impl(ctx, t, n_t, tol, obs_out, stats);
   int* const d_err = ctx->d_err_cur;

@@ -270,6 +270,35 @@ def test_mixed_context_matches_lone_registers(engine):
         np.testing.assert_allclose(tr[i], tr1[0], rtol=0, atol=1e-11)
 
 
+@pytest.mark.parametrize("case", ["mixed", "matrix"])
+def test_both_options_on_bitwise_equal_each_alone(engine, case):
+    """site_obs and pair_obs together: the aggregates, the site traces and the pair traces are bitwise
+    those of the runs with one option on (each family its own stride, arena and slot).  The mixed
+    context of test_mixed_context_matches_lone_registers and the register of test_matrix_mode."""
+    if case == "mixed":
+        dense_p = pb.build_problem(sweep_point_params(6, 75e3, "center_on", 1e-3, 7))
+        probs = [dense_p] + [_random_problem(n, 700 + n, rare_bit=n - 1) for n in (7, 12, 14)]
+        t, opts = T7, dict(dense=2, span_tile=0, matrix=0)
+    else:
+        probs, t, opts = [_p10()], np.linspace(0.0, 1e-3, 17), dict(matrix=2, dense=0)
+    obs_p, st_p, tr_p, _ = _run(engine, probs, t, pairs=1, sites=0, **opts)
+    obs_s, st_s, _, sr_s = _run(engine, probs, t, pairs=0, sites=1, **opts)
+    obs_b, st_b, tr_b, sr_b = _run(engine, probs, t, pairs=1, sites=1, **opts)
+    if case == "mixed":
+        assert st_b["dense_problems"] == 1
+    else:
+        assert st_b["mode"] == 5
+    for k in ("mode", "dense_problems", "span_problems", "real_problems", "outputs_per_launch", "tile_bits"):
+        assert st_p[k] == st_s[k] == st_b[k], k
+    assert st_b["pair_obs_problems"] == len(probs) and st_b["site_obs_problems"] == len(probs)
+    assert np.array_equal(obs_b, obs_p) and np.array_equal(obs_b, obs_s)
+    for i, p in enumerate(probs):
+        n = p.n_qubits
+        assert tr_b[i].shape == (5, n * (n - 1) // 2, len(t)) and sr_b[i].shape == (3, n, len(t))
+        assert np.array_equal(tr_b[i], tr_p[i]), i
+        assert np.array_equal(sr_b[i], sr_s[i]), i
+
+
 # ------------------------------------------------------------------------------ 7. hand-off timeout
 def test_rerun_after_handoff_timeout_overwrites(engine):
     """spin_limit = -1 fails every hand-off of the 2-tile register: the evolve re-runs on the
