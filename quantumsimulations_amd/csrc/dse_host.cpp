@@ -91,29 +91,47 @@ extern "C" int dse_bessel_j(double z, int kmax, double* out, double tol, int* de
   return DSE_OK;
 }
 
-// cheb_rows (declared in dse_internal.h, not exported): a_k = e^{-i beta tau} (2 - delta_k0) (-i)^k
-// J_k(alpha tau) of every offset tau of every set
+// cheb_series and cheb_rows (declared in dse_internal.h, not exported): a_k = e^{-i beta tau}
+// (2 - delta_k0) (-i)^k J_k(alpha tau), of one offset tau and of every offset of every set
 namespace dse {
+__attribute__((visibility("hidden")))
+int cheb_series(double alpha, double beta, double tau, double tol, double max_degree, int* deg,
+                std::vector<std::pair<double, double>>* a, int* kmax_over, std::vector<double>* J) {
+  const double z = alpha * tau;
+  const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
+  if (kmax > max_degree) {
+    *kmax_over = kmax;
+    return DSE_ERR_CONVERGENCE;
+  }
+  std::vector<double> Jv(kmax + 1);
+  int d = 1;
+  if (dse_bessel_j(z, kmax, Jv.data(), tol, &d) != DSE_OK) return DSE_ERR_ARG;
+  *deg = d;
+  const double ph = -beta * tau;
+  const std::complex<double> e(std::cos(ph), std::sin(ph));
+  std::complex<double> mi(1.0, 0.0);  // (-i)^k
+  a->assign((size_t)d + 1, std::make_pair(0.0, 0.0));
+  for (int k = 0; k <= d; ++k) {
+    const std::complex<double> ak = e * mi * ((k == 0 ? 1.0 : 2.0) * Jv[k]);
+    (*a)[k] = std::make_pair(ak.real(), ak.imag());
+    mi *= std::complex<double>(0.0, -1.0);
+  }
+  const double* j0 = Jv.data();
+  if (J) J->assign(j0, j0 + d + 1);
+  return DSE_OK;
+}
+
 __attribute__((visibility("hidden")))
 int cheb_rows(double alpha, double beta, const std::vector<std::vector<double>>& set_tau, int M, double tol,
               double max_degree, int* deg_out, std::vector<std::pair<double, double>>* rows, int* kmax_over) {
   const int n_sets = (int)set_tau.size();
   int deg = 1;
-  std::vector<std::vector<double>> J((size_t)n_sets * M);
-  std::vector<int> deg_sj((size_t)n_sets * M, 0);
+  std::vector<std::vector<std::pair<double, double>>> a((size_t)n_sets * M);
   for (int s = 0; s < n_sets; ++s)
     for (size_t j = 0; j < set_tau[s].size(); ++j) {
-      const double z = alpha * set_tau[s][j];
-      const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
-      if (kmax > max_degree) {
-        *kmax_over = kmax;
-        return DSE_ERR_CONVERGENCE;
-      }
-      std::vector<double>& Jv = J[(size_t)s * M + j];
-      Jv.resize(kmax + 1);
       int d = 1;
-      if (dse_bessel_j(z, kmax, Jv.data(), tol, &d) != DSE_OK) return DSE_ERR_ARG;
-      deg_sj[(size_t)s * M + j] = d;
+      if (int rc = cheb_series(alpha, beta, set_tau[s][j], tol, max_degree, &d, &a[(size_t)s * M + j], kmax_over, nullptr))
+        return rc;
       deg = std::max(deg, d);
     }
   *deg_out = deg;
@@ -121,18 +139,10 @@ int cheb_rows(double alpha, double beta, const std::vector<std::vector<double>>&
   rows->assign((size_t)n_sets * M * (kcap1 + 1), std::make_pair(0.0, 0.0));
   for (int s = 0; s < n_sets; ++s)
     for (size_t j = 0; j < set_tau[s].size(); ++j) {
-      const std::vector<double>& Jv = J[(size_t)s * M + j];
-      const int dj = deg_sj[(size_t)s * M + j];
-      const double ph = -beta * set_tau[s][j];
-      const std::complex<double> e(std::cos(ph), std::sin(ph));
-      std::complex<double> mi(1.0, 0.0);  // (-i)^k
+      const std::vector<std::pair<double, double>>& aj = a[(size_t)s * M + j];
       std::pair<double, double>* row = rows->data() + ((size_t)s * M + j) * (kcap1 + 1);
-      row[0] = std::make_pair((double)dj, 0.0);
-      for (int k = 0; k <= dj; ++k) {
-        const std::complex<double> a = e * mi * ((k == 0 ? 1.0 : 2.0) * Jv[k]);
-        row[1 + k] = std::make_pair(a.real(), a.imag());
-        mi *= std::complex<double>(0.0, -1.0);
-      }
+      row[0] = std::make_pair((double)(aj.size() - 1), 0.0);
+      std::copy(aj.begin(), aj.end(), row + 1);
     }
   return DSE_OK;
 }

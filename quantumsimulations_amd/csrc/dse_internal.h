@@ -17,6 +17,11 @@ namespace dse {
 // DSE_ERR_ARG when dse_bessel_j fails.  Internal to the library (hidden: not an exported symbol).
 __attribute__((visibility("hidden"))) int cheb_rows(double alpha, double beta, const std::vector<std::vector<double>>& set_tau, int M, double tol,
               double max_degree, int* deg, std::vector<std::pair<double, double>>* rows, int* kmax_over);
+// The series of one offset tau, which cheb_rows, the small-register engine and the propagator-matrix
+// mode are built on: a[k] = a_k for k <= *deg (>= 1), the same codes and *kmax_over.  J, if given:
+// dse_bessel_j's J_k(alpha tau), k <= *deg, that the a_k were made of.
+__attribute__((visibility("hidden"))) int cheb_series(double alpha, double beta, double tau, double tol, double max_degree, int* deg,
+                std::vector<std::pair<double, double>>* a, int* kmax_over, std::vector<double>* J = nullptr);
 
 enum { MODE_APPLY = 0, MODE_FIRST = 1, MODE_GEN = 2 };
 

@@ -13,369 +13,21 @@
 //   psi = B[q ? 2 : 0], acc = B[q ? 0 : 2], scratch = B1;  w_j lives in (j odd ? scratch : psi)
 // and MODE_GEN overwrites w_{k-2} in place with w_k.  At the end of the interval acc holds
 // psi(t_{m+1}) and becomes psi of the next interval.
-#include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <complex>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <numeric>
-#include <string>
-#include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <tuple>
-#include <deque>
-#include <vector>
-
+//
+// The small-register engine has a source of its own (dse_rt_small.hip); dse_ctx.h is what the runtime's
+// sources share.
 #include <unistd.h>
 
-#include <rccl/rccl.h>
-#include <rocblas/rocblas.h>
 #include <rocsolver/rocsolver.h>
 
-#include "../../include/dse.h"
-#include "dse_internal.h"
-#include "dse_dense.h"
-#include "dse_small.h"
-#include "dse_wht.h"
+#include "dse_ctx.h"
 
 using namespace dse;
-
-namespace {
-
-struct HostProblem {
-  int n = 0;
-  std::vector<double> field, zz, pair, flip;
-  double shift = 0.0;
-  uint64_t psi0 = 0, sea_mask = 0;
-  int rare_bit = -1;
-  double rare_z = 0.0;
-  double e_min = 0.0, e_max = 0.0;
-  // device state
-  int L = 0;
-  int64_t n_tiles = 0;
-  double2* buf[3] = {nullptr, nullptr, nullptr};
-  void* tables = nullptr;
-  double2* coef = nullptr;   // into dse_ctx::d_coef (compact rows, coef_row)
-  int degree = 1;
-  double flops_per_amp = 0.0;  // algorithmic flops of one H application per amplitude
-  int2* d_items = nullptr;  // this problem's tiles (apply_h / observables hooks)
-  // partitioned register (dse_add_problem_sharded): shard `shard_rank` of 2^shard_bits
-  int shard_bits = 0, shard_rank = 0;
-  int n_local = 0;           // qubits held by this shard (n - shard_bits)
-  int group_first = -1;      // loopback group: index of shard 0 (all shards in this context)
-  bool dist = false;         // shard of a register partitioned over processes (RCCL exchange)
-  uint32_t xmasks = 0;       // bit m set: terms or observables read shard rank ^ m
-  double2* rbuf_own[kMaxShards] = {};  // dist: receive buffers of the exchange, per mask
-  bool imag = false;         // every drive coefficient purely imaginary (drive phase pi/2)
-  // Walsh-Hadamard engine (dse_wht.hip): X- and Y-branch vectors and the pair matrix
-  double2* wvec[4] = {nullptr, nullptr, nullptr, nullptr};  // A, B (+ index-swapped A, B)
-  double* d_cquad = nullptr;
-  double* d_wtab = nullptr;  // ztab | xytab
-  int wht_groups = 0;        // passes' tile-bit groups; 0: this problem uses the step kernels
-  // small-register engine (dse_small.hip): n <= 9 qubits, whole evolution one wave per problem
-  bool sm = false;           // this evolve runs the problem on that engine
-  // dense eigen-propagator engine (dse_dense.hip): this evolve diagonalises the register instead
-  bool dn = false;
-  // propagator-matrix mode (matrix_run): the context's single register, U = exp(-iH dt) built
-  // column by column, the outputs by repeated products
-  bool mx = false;
-  bool side() const { return sm || dn || mx; }  // not on the per-interval Chebyshev launches
-  double2* sm_coef = nullptr;  // into dse_ctx::d_sm_coef
-  int* sm_deg = nullptr;
-  int final_bsel = 0;        // buffer holding the final state after dse_evolve
-  // spanning register (dse_span.hip): this evolve runs the register over 2^span_s workgroups of
-  // 2^(n - span_s) amplitudes (0: not spanned)
-  int span_s = 0;
-  // real-component mode (dse_real.hip): this evolve runs the register as two real recurrences
-  bool rl = false;
-  // custom psi(t0) (ABI 14.1; every shard of a loopback register alike): 0 the basis state psi0; 1 a
-  // stored state in init_state (this shard's 2^n_local amplitudes: the one extra state-sized
-  // buffer, held only while the problem has a stored state); 2 a product state, its 4 n amplitudes
-  // in init_amp and on the device in d_init_amp.  They belong to the problem: kept over evolves and
-  // over free_device, released by dse_clear / dse_destroy or when the kind changes
-  int init_kind = 0;
-  double2* init_state = nullptr;
-  std::vector<double> init_amp;
-  double* d_init_amp = nullptr;
-};
-
-int fail(dse_ctx* c, int code, const std::string& msg);
-
-// One grow-only device buffer of cap elements.  reserve() keeps a buffer that is large enough and
-// otherwise frees it before it allocates the larger one (the contents are not kept); after a failed
-// allocation the buffer is empty, cap = 0.
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;  // in elements
-  void release() {
-    if (p) (void)hipFree(p), p = nullptr;
-    cap = 0;
-  }
-  // what: the message of DSE_ERR_OOM; with_bytes appends " (<size> bytes)"
-  int reserve(dse_ctx* ctx, size_t n, const char* what, bool with_bytes = false) {
-    if (n <= cap) return DSE_OK;
-    release();
-    if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) {
-      p = nullptr;
-      return fail(ctx, DSE_ERR_OOM, with_bytes ? std::string(what) + " (" + std::to_string(n * sizeof(T)) + " bytes)" : what);
-    }
-    cap = n;
-    return DSE_OK;
-  }
-};
-template <class... B>
-void release_all(B&... b) { (b.release(), ...); }
-
-// The observable families beside the seven aggregates: sums per unit (register bit, pair of bits)
-// of every output state, kept per register and read back after the evolve.  kObsFamilies below
-// describes each; the engines launch them in this order and read them back in the reverse one.
-enum ObsFamily { kSite = 0, kPair = 1, kNumObsFamilies = 2 };
-constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair};
-constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kPair, kSite};
-
-// What a context holds for one family: its option, a partial arena for the tile engine's kernel
-// (S doubles per tile and slot: the family's stride of the context's widest register), and the
-// results of the last evolve, per register [comps][units][n_t] (loopback group: shard 0's entry)
-struct ObsFamilyState {
-  int on = 0;
-  DevBuf<double> d_partial;
-  size_t slots = 0;
-  int S = 0;
-  std::vector<std::vector<double>> store;
-  int nt = 0;              // output times of store (0: none)
-  int problems = 0;        // registers with sums in the last successful evolve
-  DevBuf<double> d_small;  // small engine: [problem][n_t][small_stride] raw sums
-  void release() {
-    release_all(d_partial, d_small);
-    slots = 0;
-    store.clear();
-    nt = problems = 0;
-  }
-};
-
-// What a lane group launches.  Tiles: k_interval (persistent) or the step / Walsh-Hadamard kernels (streaming)
-// over problems of `tiles` tiles each; Mixed: 1- and 2-tile problems in one k_interval launch; Span: k_span; Real: k_real
-enum class GroupKind { Tiles, Mixed, Span, Real };
-
-// One stream's share of the problems, grouped by tile size.
-struct LaneGroup {
-  int L = 0;
-  GroupKind kind = GroupKind::Tiles;
-  int tiles = 1;            // tiles per problem of kind Tiles (persistent mode: 1 or 2); else 0
-  int wht_groups = 0;       // > 0: every problem of the group runs on the Walsh-Hadamard engine
-  std::vector<std::pair<int, int>> wht_regs;  // partitioned registers: (first shard, degree)
-  int64_t off = 0;          // first position in the global item array
-  int64_t count = 0;        // items of this group
-  std::vector<int> active;     // active[k] = items with degree >= k (prefix of the group)
-  std::vector<double> bytes;   // bytes[k] = algorithmic HBM bytes of the term-k launch
-  std::vector<double> flops;   // flops[k] = algorithmic flops of the term-k launch
-  // spanning registers (kind Span): k_span<span_L, span_rb> over span_count launch items from
-  // span_off in dse_ctx::d_span_items (tiles of one register 8 apart, padding items x = -1)
-  int span_L = 0, span_rb = 0;
-  int64_t span_off = 0, span_count = 0;
-  // launch boundaries inside those items (relative to span_off, last = span_count): whole blocks of
-  // 8 registers, each launch at most what the chip holds at once (every register's tiles resident
-  // together: its hand-offs wait on each other)
-  std::vector<int64_t> span_cuts;
-  std::vector<double> span_am, span_fl;  // per launch: amplitudes x terms, algorithmic flops
-  // real-component registers: k_real over real_count items (problem, component) from real_off in
-  // dse_ctx::d_real_items, then k_real_combine over real_np items (problem, 0) from real_poff
-  int64_t real_off = 0, real_count = 0, real_poff = 0, real_np = 0;
-};
-struct Lane {
-  hipStream_t stream = nullptr;
-  // persistent mode, option obs_overlap: the observables of interval group g run on obs_stream
-  // behind ev_iv[g & 1] (its interval launches), and interval group g + 2, which rewrites the
-  // buffers they read, waits for ev_obs[g & 1]
-  hipStream_t obs_stream = nullptr;
-  hipEvent_t ev_iv[2] = {nullptr, nullptr}, ev_obs[2] = {nullptr, nullptr};
-  bool obs_pending[2] = {false, false};
-  std::vector<LaneGroup> groups;
-  std::vector<hipEvent_t> ev[2];
-  size_t ev_used[2] = {0, 0};
-  int max_deg = 0;
-};
-
-}  // namespace
-
-// internal return code of evolve_impl: a persistent hand-off timed out (dse_evolve falls back)
-constexpr int kRcHandoffTimeout = 1000;
-
-struct dse_ctx {
-  int device = 0;
-  std::string err;
-  std::vector<HostProblem> probs;
-  DevProb* d_probs = nullptr;
-  std::vector<DevProb> h_desc;
-  std::vector<Lane> lanes;
-  int2* d_items = nullptr;          // all items, lane-major, degree-sorted inside each group
-  int2* d_items_iv = nullptr;       // the same, 2-tile groups reordered for the interval kernel
-  std::vector<int64_t> item_pos;    // first item position of every problem (evolve layout)
-  int64_t total_items = 0;
-  DevBuf<double> d_partial;
-  size_t partial_slots = 0;
-  // site-resolved observables and two-spin correlators (kObsFamilies), indexed by ObsFamily
-  ObsFamilyState fam[kNumObsFamilies];
-  std::map<std::vector<double>, double*> zzlo_tables;  // identical in-tile ZZ tables are shared
-  bool prepared = false;
-  bool evolved = false;
-  bool final_valid = false;         // the last dse_evolve returned DSE_OK (dse_continue_from_final)
-  int last_q = 0;
-  int tile_bits = 13;
-  int n_streams = 4;
-  int persistent = 1;               // use k_interval when every problem fits <= 2 tiles
-  int wht = 1;                      // Walsh-Hadamard engine for registers of more tiles
-  int wht_group_bits = 0;           // high bits per pass of that engine (0: tile bits - 2)
-  int wht_tile_bits = 0;            // its tile: 12, 13 (0 = 13)
-  int wht_persist = 0;              // bit 1: MID as a persistent launch (k_wht_mid_p), option wht_persist
-  int wht_contiguous = 0;           // option wht_contiguous: hipDeviceMallocContiguous X/Y vectors
-  int wht_fuse = 1;                 // option wht_fuse: FINAL of term k runs term k + 1's FIRST
-  int wht_mid_inpage = 0;           // option wht_mid_inpage: in-page high bits of the MID group
-  int wht_half = 7;                 // option wht_half: half-LDS passes (k_wht_h), bit 0 FIRST, 1 FWD/INV, 2 MID
-  WhtProb* d_wht = nullptr;         // per problem (zero entries: not on that engine)
-  bool wht_ready = false;
-  int xcd_pairs = 1;                // diagnostics: 0 keeps the two tiles of a problem adjacent
-  int mixed_launch = 1;             // persistent: 1- and 2-tile problems of one tile size in one launch
-  int span_partial = 1;             // option span_partial: the auto span policy's partial form
-  int span_chunks = 2;              // option span_chunks: resident launches the auto policy allows (0-2)
-  int span_partial_tile = 11;       // option span_partial_tile: the partial form's tile (10, 11)
-  int obs_overlap = 0;              // persistent: observables off the interval launches' stream
-  int n_cu = 256;                   // compute units of the device
-  int coresident = 0;               // diagnostics: workgroups per 2-tile interval chunk (0: occupancy)
-  int handoff_fallbacks = 0;        // this evolve call re-ran on the streaming kernels after a hand-off timeout (0/1)
-  bool rerun = false;               // that re-run: the dense engine's results of the first pass are kept
-  int* d_err_cur = nullptr;         // the hand-off error word of the running persistent evolve (else null)
-  DevBuf<double> d_allreduce;       // RCCL all-reduce staging buffer of the observable sums
-  DevBuf<int> d_flags;              // hand-off flags (2 tiles x kIvWaves per problem) + error word
-  DevBuf<double2> d_xslots;         // hand-off slots of the interval kernel
-  DevBuf<double2> d_xacc;           // intermediate outputs of multi-output launches
-  // per-evolve uploads, one device arena each (one copy per evolve, not one per problem)
-  DevBuf<unsigned char> d_coef;     // Chebyshev coefficient rows of every problem
-  DevBuf<unsigned char> d_sm_coef;  // small-engine coefficients and degrees
-  DevBuf<BasisInit> d_init;         // psi(t0) list
-  int outputs_per_launch = 2;       // M of the interval kernel (dse_evolve picks 1 on coarse grids)
-  int span_outputs = 4;             // M when every register spans (k_span, staggered sums)
-  int64_t probe_items = 0;          // 0: all items
-  int time_every = 1;               // 0: no kernel timing; N: time intervals with m % N == 0
-  double max_degree = 2e6;
-  // partitioned registers over processes: one RCCL communicator, one rank per GPU
-  ncclComm_t comm = nullptr;
-  int dist_rank = 0, dist_world = 1;
-  // or a host transport (dse_dist_init_exchange): device data staged through host buffers
-  dse_exchange_fn xfn = nullptr;
-  void* xuser = nullptr;
-  std::vector<unsigned char> xsend, xrecv;
-  double xbytes = 0.0;              // bytes this rank sent to other ranks (current evolve)
-  // exchange timing (current evolve): HIP event pairs around RCCL calls (summed at the end of
-  // dse_evolve) plus host wall time of host-transport exchanges
-  std::vector<hipEvent_t> xev;
-  size_t xev_used = 0;
-  double xms = 0.0;
-  // small-register engine
-  int dbg = 0;                      // diagnostics switches (option "dbg")
-  int small = 1;                    // registers of <= 9 qubits run on dse_small.hip
-  int small_chunk = 64;             // output intervals per launch of that engine
-  hipStream_t small_stream = nullptr;
-  // partitioned registers on the Walsh-Hadamard engine: the index swaps run on swap_stream, one
-  // vector's swap under the other vector's pass (option "swap_overlap"); swap_ev orders the two
-  int swap_overlap = 1;
-  hipStream_t swap_stream = nullptr;
-  hipEvent_t swap_ev[8] = {};
-  DevBuf<SmallProb> d_small;        // descriptors
-  DevBuf<double> d_small_out;       // [problem][n_t][8] raw observable sums
-  DevBuf<int> d_small_aux;          // problem selections per register size, interval -> set map
-  // dense eigen-propagator engine (dse_dense.h): option "dense" 0 off, 1 when cheaper than the
-  // Chebyshev propagator by the cost model of dense_cheaper (default), 2 for every eligible register
-  int dense = 1;
-  // propagator-matrix mode for a context holding one register on a uniform grid: 0 off, 1 when
-  // the model of matrix_cheaper says so (default), 2 whenever eligible
-  int matrix = 1;
-  // matrix mode's device buffers (U, the states, the products' partial sums, tables), kept across
-  // evolves of the same register size (simulate_rare calls one register at a time; a 2^12 register
-  // holds 256 MiB of U) and released by dse_destroy or when a larger register needs more
-  DevBuf<unsigned char> d_mx;
-  // option "symv_fused": each product's reduction inside the product's launch (agent-scope counters
-  // with a release per workgroup): measured 22.9 vs 10.4 ms for config 2, so off by default
-  int symv_fused = 0;
-  double mx_build_ms = 0.0, mx_products_ms = 0.0, mx_products = 0.0, mx_bytes_per_product = 0.0;  // last matrix_run
-
-  // spanning registers (dse_span.hip): option "span" 0 off; s = 1..4: every register that fits
-  // runs over 2^s workgroups (one per CU) of 2^(n - s) amplitudes; "span_rb": amplitudes per
-  // thread 2^span_rb (0: 512 threads per workgroup)
-  int span = 0;
-  int span_tile = -1;               // option "span_tile": L > 0 every register of n > L qubits spans 2^(n-L)
-                                    // tiles; -1 (default) auto: L = 11 when all tiles fit the chip at once
-  // real-component mode (dse_real.hip, option "real", default 0): registers of 13 or 14 qubits with
-  // imaginary drives run as two real recurrences, one workgroup per component, no hand-off
-  int real_mode = 0;
-  DevBuf<double2> d_real;           // [a | b] inputs and propagator sums of the real-mode registers
-  DevBuf<unsigned char> d_real_tab;
-  DevBuf<int2> d_real_items;
-  int span_rb = 0;
-  DevBuf<SpanDesc> d_span;          // per problem
-  DevBuf<unsigned char> d_span_tab;
-  DevBuf<double2> d_span_slots;     // hand-off slots of the spanned registers
-  DevBuf<int> d_span_flags;
-  DevBuf<int2> d_span_items;
-
-  hipStream_t dense_stream = nullptr;
-  rocblas_handle blas = nullptr;
-  // dense engine: registers of >= 2^10 amplitudes are diagonalised up to eig_streams at a time (one
-  // host thread, stream and rocBLAS handle each; option "eig_streams", default 3: one N = 14 point
-  // of the 30 s grid (two 2^14 registers through the two-stage solver, one 2^13) 4.54 / 4.00 / 3.75 /
-  // 3.87 s with 1 / 2 / 3 / 4 streams, profiles/r04/eig_streams_point_2stage.jsonl)
-  int eig_streams = 3;
-  // dense engine eigensolver: 0 rocSOLVER dsyevd at every size; 1 eig_sym_lower (dse_sytrd.hip: the
-  // half-matrix tridiagonalisation from 2^13, rocSOLVER dstedc, the blocked back-transformation)
-  // from kEigHalfMinDim amplitudes, dsyevd below; 2 eig_sym_lower from 2^10 (tests)
-  int eig_impl = 1;
-  // the two-stage eigensolver's cross-workgroup polls give up after this many rounds (option
-  // eig_spin_limit; < 0: at once, tests); a give-up re-solves that register with dsyevd
-  int eig_spin = kEig2DefaultSpin;
-  HandoffKnobs hk;  // options spin_limit, handoff_fences: every persistent launch of this context
-  std::atomic<int> eig_fallbacks{0};  // registers re-solved that way in the last evolve
-  // dense engine: eigenvalues refined by double-double Rayleigh quotients and output phases reduced
-  // in double-double (option "dense_refine", default 1; 0: the eigensolver's eigenvalues and fp64
-  // phases, whose error grows like eps |lambda| t: ~1e-8 at the reference grid's 30 s)
-  int dense_refine = 1;
-  // dense engine: output times of registers of >= kNufftMinDim amplitudes by a type-1 non-uniform
-  // FFT on uniform grids (option "dense_nufft": 1 default, from kNufftMinOutputs outputs; 2 every
-  // register from two outputs (tests); 0 the [cos | -sin] GEMM for every output), dse_nufft.hip;
-  // its rocFFT plans
-  int dense_nufft = 1;
-  NufftCache* nufft = nullptr;
-  int nufft_problems = 0;     // last evolve: registers whose outputs came from the transform
-  double dense_out_ms = 0.0;  // last evolve: host wall time of the dense engine's output stage
-  std::vector<hipStream_t> eig_st;
-  std::vector<rocblas_handle> eig_h;
-};
+using namespace dse::rt;
 
 namespace {
 
 thread_local std::string g_create_err;
-
-int fail(dse_ctx* c, int code, const std::string& msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
-#define HIPC(expr)                                                                      \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess)                                                               \
-      return fail(ctx, DSE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Host worker threads kept for the process (created on first use, never joined: they only wait
 // on a condition variable between jobs), so a dse_evolve does not pay ~16 thread creations per
@@ -457,21 +109,9 @@ void parallel_for(size_t n, F&& f) {
   for (auto& x : th) x.join();
 }
 
-// Host bytes gathered for one upload: pieces 64-B aligned, offsets into the device arena.
-struct Arena {
-  std::vector<unsigned char> host;
-  size_t add(const void* src, size_t bytes) {
-    const size_t off = place(bytes);
-    if (bytes) std::memcpy(host.data() + off, src, bytes);
-    return off;
-  }
-  size_t place(size_t bytes) {  // room for a piece filled later
-    const size_t off = align_up(host.size(), 64);
-    host.resize(off + bytes);
-    return off;
-  }
-};
+}  // namespace
 
+namespace dse::rt {
 // The arena's device copy: grows dev to fit, then one copy on stream st (stream-ordered before
 // every later launch on st; the caller synchronises st before other streams use it).
 int upload_arena(dse_ctx* ctx, const Arena& a, DevBuf<unsigned char>& dev, hipStream_t st) {
@@ -481,6 +121,9 @@ int upload_arena(dse_ctx* ctx, const Arena& a, DevBuf<unsigned char>& dev, hipSt
   HIPC(hipStreamSynchronize(st));  // the host bytes may be released after return
   return DSE_OK;
 }
+}  // namespace dse::rt
+
+namespace {
 
 void free_wht(HostProblem& p) {
   for (auto& b : p.wvec)
@@ -1214,33 +857,6 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
 
 // ---- observable families: site-resolved observables and two-spin correlators ------------------
 
-// One family: raw sums v of a register, comps per unit at v[comps * u + c] and ||psi||^2 at
-// v[comps * units], `stride` doubles per state; results normalised by that norm.
-struct ObsFamilyDesc {
-  const char *option, *hook, *noun;  // the option's and the hook's names, the family's word in messages
-  int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index)
-  int (*units)(int n);
-  int (*stride)(int n);
-  int small_stride;                                        // the small engine's stride (its widest register's)
-  decltype(&launch_obs_sites) launch;                      // tile engine: S >= stride(n) doubles per tile
-  decltype(&launch_dense_obs_sites) launch_dense;          // dense engine, batched
-  decltype(&launch_dense_obs_sites_c) launch_dense_c;      // dense engine and matrix mode: one register, interleaved columns
-  double* DenseProb::*dense_out;                           // where those two write
-  // Where the twins differ.  The site hook refuses only its own register when that is a dist shard,
-  // before prepare; the pair hook refuses as the option does (obs_family_refusal), after it
-  bool hook_refuses_shard_early;
-  // refusal when one output slot of the arena exceeds kPartialCapBytes (pair: up to 2806 doubles per
-  // tile; the site arena, at most 104 per tile, takes one slot per flush then)
-  bool slot_cap;
-  bool get_needs_option;  // the getter refuses once the option is back at 0 (site: serves the last record)
-};
-const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
-    {"site_obs", "dse_site_observables", "site", 3, [](int n) { return n; }, [](int n) { return site_stride(n); },
-     kSmallSiteStride, launch_obs_sites, launch_dense_obs_sites, launch_dense_obs_sites_c, &DenseProb::sites, true, false, false},
-    {"pair_obs", "dse_pair_observables", "pair", 5, [](int n) { return n * (n - 1) / 2; },
-     [](int n) { return pair_stride(n); }, kSmallPairStride, launch_obs_pairs, launch_dense_obs_pairs,
-     launch_dense_obs_pairs_c, &DenseProb::pairs, false, true, true},
-};
 
 // Refusals of the option and of the hook (`who`), decided before any work (after prepare: the tile
 // count is known): no register partitioned over processes, and with slot_cap one output slot of the
@@ -1283,11 +899,17 @@ void finish_family(const ObsFamilyDesc& F, int n, const double* v, double* o, si
     for (int c = 0; c < F.comps; ++c) o[((size_t)c * units + u) * stride] = v[F.comps * u + c] * inv;
 }
 
+}  // namespace
+
+namespace dse::rt {
 // finish_family for register pi's outputs 0 .. n_t - 1, raw sums `stride` doubles apart, into its store
 void finish_family_outputs(dse_ctx* ctx, ObsFamily f, size_t pi, const double* raw, size_t stride, int n_t) {
   for (int ti = 0; ti < n_t; ++ti)
     finish_family(kObsFamilies[f], ctx->probs[pi].n, raw + ti * stride, ctx->fam[f].store[pi].data() + ti, (size_t)n_t);
 }
+}  // namespace dse::rt
+
+namespace {
 
 size_t obs_store_size(ObsFamily f, const HostProblem& P, int n_t) {
   return (size_t)kObsFamilies[f].comps * kObsFamilies[f].units(P.n) * n_t;
@@ -1340,6 +962,9 @@ int flush_family_partials(dse_ctx* ctx, ObsFamily f, size_t nslots, size_t t0, i
   return DSE_OK;
 }
 
+}  // namespace
+
+namespace dse::rt {
 void finish_obs(const HostProblem& P, const double* v, double* o, size_t stride) {
   const double n2 = v[6];
   const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
@@ -1351,6 +976,9 @@ void finish_obs(const HostProblem& P, const double* v, double* o, size_t stride)
   o[5 * stride] = P.rare_bit >= 0 ? v[5] * inv : 0.0;
   o[6 * stride] = std::sqrt(n2);
 }
+}  // namespace dse::rt
+
+namespace {
 
 // Observable sums of output slots [t0, t0 + nslots).  A loopback shard group sums the tiles of all
 // its shards and writes the result to every shard's row; a dist shard keeps its raw local sums in
@@ -1452,6 +1080,105 @@ int ensure_events(dse_ctx* ctx, Lane& ln, size_t per_pool) {
   return DSE_OK;
 }
 
+// ---- options (dse_set_option) -------------------------------------------------------------------
+// How a value is checked, and what it is stored as
+enum class OptCheck {
+  Bool,   // any value, NaN too: stored as value != 0.0
+  Int,    // any value: stored as (int)value
+  Range,  // lo <= value <= hi or one of `also`, else the message: stored as (int)value
+  Whole,  // the same, the values of the range whole numbers
+};
+// Reset: the device layout depends on the option, so when its stored value changes the context's
+// streams are drained and its device state is released first (rebuilt by the next prepare)
+enum class OptEffect { Store, Reset };
+
+constexpr double kNoValue = std::numeric_limits<double>::quiet_NaN();  // in `also`: equals no value
+
+struct Option {
+  const char* key;
+  int dse_ctx::*field;
+  OptCheck check;
+  OptEffect effect = OptEffect::Store;
+  double lo = 0.0, hi = 0.0;
+  std::string msg;
+  double also[2] = {kNoValue, kNoValue};
+};
+
+bool option_accepts(const Option& o, double value) {
+  if (o.check == OptCheck::Bool || o.check == OptCheck::Int) return true;
+  if (value >= o.lo && value <= o.hi && (o.check == OptCheck::Range || value == (int)value)) return true;
+  return value == o.also[0] || value == o.also[1];
+}
+
+// Every option that is one int of the context.  streams, the observable families, the hand-off
+// knobs, the ablation masks, probe_items and max_degree are not: dse_set_option spells them out.
+const Option kOptions[] = {
+    {"tile_bits", &dse_ctx::tile_bits, OptCheck::Range, OptEffect::Reset, 1, kMaxTile, "tile_bits must be in 1..13"},
+    {"persistent", &dse_ctx::persistent, OptCheck::Bool},
+    {"swap_overlap", &dse_ctx::swap_overlap, OptCheck::Bool},
+    {"wht", &dse_ctx::wht, OptCheck::Bool, OptEffect::Reset},
+    // Walsh-Hadamard engine's vectors physically contiguous
+    {"wht_contiguous", &dse_ctx::wht_contiguous, OptCheck::Whole, OptEffect::Reset, 0, 1, "wht_contiguous must be 0 or 1"},
+    // Walsh-Hadamard engine: FINAL of term k + FIRST of term k + 1
+    {"wht_fuse", &dse_ctx::wht_fuse, OptCheck::Whole, OptEffect::Store, 0, 1, "wht_fuse must be 0 or 1"},
+    // Walsh-Hadamard plan: MID group's high bits below the page
+    {"wht_mid_inpage", &dse_ctx::wht_mid_inpage, OptCheck::Whole, OptEffect::Reset, 0, 8, "wht_mid_inpage must be 0..8"},
+    // Walsh-Hadamard passes through half the LDS, two workgroups per CU
+    {"wht_half", &dse_ctx::wht_half, OptCheck::Whole, OptEffect::Store, 0, 7, "wht_half must be 0..7"},
+    // Walsh-Hadamard passes as persistent launches: bit 1 MID
+    {"wht_persist", &dse_ctx::wht_persist, OptCheck::Int},
+    {"wht_tile_bits", &dse_ctx::wht_tile_bits, OptCheck::Whole, OptEffect::Reset, 12, 13, "wht_tile_bits must be 0, 12 or 13", {0, kNoValue}},
+    {"wht_group_bits", &dse_ctx::wht_group_bits, OptCheck::Range, OptEffect::Reset, 2, 11, "wht_group_bits must be 0 or in 2..11", {0, kNoValue}},
+    {"outputs_per_launch", &dse_ctx::outputs_per_launch, OptCheck::Range, OptEffect::Store, 1, kMaxOut,
+     "outputs_per_launch must be in 1.." + std::to_string(kMaxOut)},
+    // M of an evolve whose registers all span (k_span)
+    {"span_outputs", &dse_ctx::span_outputs, OptCheck::Range, OptEffect::Store, 1, kSpanMaxOut,
+     "span_outputs must be in 1.." + std::to_string(kSpanMaxOut)},
+    // diagnostics: workgroups per chunk of a 2-tile interval launch
+    {"coresident", &dse_ctx::coresident, OptCheck::Range, OptEffect::Store, 2, 4096, "coresident must be 0 or in 2..4096", {0, kNoValue}},
+    // diagnostics bit mask: 1 one observable launch per output, 2 psi0 by memset/copy, 4 coefficient
+    // tables on one host thread
+    {"dbg", &dse_ctx::dbg, OptCheck::Int},
+    // registers of <= 9 qubits on the one-wave engine (dse_small.hip)
+    {"small", &dse_ctx::small, OptCheck::Bool},
+    // propagator-matrix mode: 0 off, 1 auto, 2 always (when eligible)
+    {"matrix", &dse_ctx::matrix, OptCheck::Whole, OptEffect::Store, 0, 2, "matrix must be 0, 1 or 2"},
+    // dense engine: large eigendecompositions at a time (1..8)
+    {"eig_streams", &dse_ctx::eig_streams, OptCheck::Range, OptEffect::Store, 1, 8, "eig_streams must be in 1..8"},
+    // dense engine eigensolver: 0 dsyevd, 1 auto, 2 half-matrix from 2^10, 3 two-stage from 2^10
+    {"eig_impl", &dse_ctx::eig_impl, OptCheck::Range, OptEffect::Store, 0, 3, "eig_impl must be 0, 1, 2 or 3"},
+    // two-stage eigensolver: poll rounds before a give-up (< 0: at once)
+    {"eig_spin_limit", &dse_ctx::eig_spin, OptCheck::Range, OptEffect::Store, -1, 1 << 30, "eig_spin_limit must be in -1..2^30"},
+    // dense engine: refined eigenvalues + double-double phases
+    {"dense_refine", &dse_ctx::dense_refine, OptCheck::Bool},
+    // dense engine: output times by the non-uniform FFT (0, 1, 2)
+    {"dense_nufft", &dse_ctx::dense_nufft, OptCheck::Whole, OptEffect::Store, 0, 2, "dense_nufft must be 0, 1 or 2"},
+    // matrix mode: each product's reduction in the product's launch
+    {"symv_fused", &dse_ctx::symv_fused, OptCheck::Bool},
+    // dense eigen-propagator engine: 0 off, 1 auto (cost model), 2 always
+    {"dense", &dse_ctx::dense, OptCheck::Whole, OptEffect::Store, 0, 2, "dense must be 0, 1 or 2"},
+    {"small_chunk", &dse_ctx::small_chunk, OptCheck::Range, OptEffect::Store, 1, 1e6, "small_chunk must be in 1..1e6"},
+    {"xcd_pairs", &dse_ctx::xcd_pairs, OptCheck::Bool},
+    // spanning registers: 0 off, 1..4 top bits (workgroups 2^s per register)
+    {"span", &dse_ctx::span, OptCheck::Range, OptEffect::Store, 0, kSpanMaxTop, "span must be in 0..4"},
+    // real-component mode for registers of 13 / 14 qubits (imaginary drives)
+    {"real", &dse_ctx::real_mode, OptCheck::Whole, OptEffect::Store, 0, 2, "real must be 0, 1 or 2"},
+    // spanning registers: tile bits L (0 off, -1 auto); n > L qubits span 2^(n-L) tiles
+    {"span_tile", &dse_ctx::span_tile, OptCheck::Range, OptEffect::Store, 10, 13, "span_tile must be -1, 0 or in 10..13", {0, -1}},
+    // amplitudes per thread of k_span: 2^span_rb (0: 512 threads)
+    {"span_rb", &dse_ctx::span_rb, OptCheck::Range, OptEffect::Store, 0, 3, "span_rb must be in 0..3"},
+    // auto span policy: span the stiffest registers beside k_interval
+    {"span_partial", &dse_ctx::span_partial, OptCheck::Bool},
+    // auto span policy: resident launches per interval for all-span
+    {"span_chunks", &dse_ctx::span_chunks, OptCheck::Whole, OptEffect::Store, 0, 2, "span_chunks must be 0, 1 or 2"},
+    // auto span policy, partial form: log2 tile (10, 11)
+    {"span_partial_tile", &dse_ctx::span_partial_tile, OptCheck::Whole, OptEffect::Store, 10, 11, "span_partial_tile must be 10 or 11"},
+    {"mixed_launch", &dse_ctx::mixed_launch, OptCheck::Bool},
+    {"obs_overlap", &dse_ctx::obs_overlap, OptCheck::Bool},
+    {"time_kernels", &dse_ctx::time_every, OptCheck::Range, OptEffect::Store, 0, std::numeric_limits<double>::infinity(),
+     "time_kernels must be >= 0"},
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -1533,14 +1260,18 @@ int dse_set_option(dse_ctx* ctx, const char* key, double value) {
   if (!ctx || !key) return DSE_ERR_ARG;
   const std::string k(key);
   (void)hipSetDevice(ctx->device);
-  if (k == "tile_bits") {
-    if (!(value >= 1 && value <= kMaxTile)) return fail(ctx, DSE_ERR_ARG, "tile_bits must be in 1..13");
-    if ((int)value != ctx->tile_bits) {
+  for (const Option& o : kOptions) {
+    if (k != o.key) continue;
+    if (!option_accepts(o, value)) return fail(ctx, DSE_ERR_ARG, o.msg);
+    const int v = o.check == OptCheck::Bool ? value != 0.0 : (int)value;
+    if (o.effect == OptEffect::Reset && v != ctx->*o.field) {
       (void)sync_all(ctx);
       free_device(ctx);
-      ctx->tile_bits = (int)value;
     }
-  } else if (k == "streams") {
+    ctx->*o.field = v;
+    return DSE_OK;
+  }
+  if (k == "streams") {
     if (!(value >= 1 && value <= 16)) return fail(ctx, DSE_ERR_ARG, "streams must be in 1..16");
     (void)sync_all(ctx);
     ctx->n_streams = (int)value;
@@ -1549,131 +1280,11 @@ int dse_set_option(dse_ctx* ctx, const char* key, double value) {
   } else if (k == kObsFamilies[kSite].option || k == kObsFamilies[kPair].option) {  // beside the seven aggregates
     if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, k + " must be 0 or 1");
     ctx->fam[k == kObsFamilies[kSite].option ? kSite : kPair].on = (int)value;
-  } else if (k == "persistent") {
-    ctx->persistent = value != 0.0;
-  } else if (k == "swap_overlap") {
-    ctx->swap_overlap = value != 0.0;
-  } else if (k == "wht") {
-    if ((value != 0.0) != (ctx->wht != 0)) {
-      (void)sync_all(ctx);
-      free_device(ctx);
-      ctx->wht = value != 0.0;
-    }
-  } else if (k == "wht_contiguous") {  // Walsh-Hadamard engine's vectors physically contiguous
-    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "wht_contiguous must be 0 or 1");
-    if ((int)value != ctx->wht_contiguous) {
-      (void)sync_all(ctx);
-      free_device(ctx);
-      ctx->wht_contiguous = (int)value;
-    }
-  } else if (k == "wht_fuse") {  // Walsh-Hadamard engine: FINAL of term k + FIRST of term k + 1
-    if (!(value == 0.0 || value == 1.0)) return fail(ctx, DSE_ERR_ARG, "wht_fuse must be 0 or 1");
-    ctx->wht_fuse = (int)value;
-  } else if (k == "wht_mid_inpage") {  // Walsh-Hadamard plan: MID group's high bits below the page
-    if (!(value >= 0.0 && value <= 8.0 && value == (int)value)) return fail(ctx, DSE_ERR_ARG, "wht_mid_inpage must be 0..8");
-    if ((int)value != ctx->wht_mid_inpage) {
-      (void)sync_all(ctx);
-      free_device(ctx);
-      ctx->wht_mid_inpage = (int)value;
-    }
-  } else if (k == "wht_half") {  // Walsh-Hadamard passes through half the LDS, two workgroups per CU
-    if (!(value >= 0.0 && value <= 7.0 && value == (int)value)) return fail(ctx, DSE_ERR_ARG, "wht_half must be 0..7");
-    ctx->wht_half = (int)value;
-  } else if (k == "wht_persist") {  // Walsh-Hadamard passes as persistent launches: bit 1 MID
-    ctx->wht_persist = (int)value;
-  } else if (k == "wht_tile_bits") {
-    if (!(value == 0 || value == 12 || value == 13)) return fail(ctx, DSE_ERR_ARG, "wht_tile_bits must be 0, 12 or 13");
-    if ((int)value != ctx->wht_tile_bits) {
-      (void)sync_all(ctx);
-      free_device(ctx);
-      ctx->wht_tile_bits = (int)value;
-    }
-  } else if (k == "wht_group_bits") {
-    if (!(value == 0 || (value >= 2 && value <= 11)))
-      return fail(ctx, DSE_ERR_ARG, "wht_group_bits must be 0 or in 2..11");
-    if ((int)value != ctx->wht_group_bits) {
-      (void)sync_all(ctx);
-      free_device(ctx);
-      ctx->wht_group_bits = (int)value;
-    }
-  } else if (k == "outputs_per_launch") {
-    if (!(value >= 1 && value <= kMaxOut))
-      return fail(ctx, DSE_ERR_ARG, "outputs_per_launch must be in 1.." + std::to_string(kMaxOut));
-    ctx->outputs_per_launch = (int)value;
-  } else if (k == "span_outputs") {  // M of an evolve whose registers all span (k_span)
-    if (!(value >= 1 && value <= kSpanMaxOut))
-      return fail(ctx, DSE_ERR_ARG, "span_outputs must be in 1.." + std::to_string(kSpanMaxOut));
-    ctx->span_outputs = (int)value;
-  } else if (k == "coresident") {  // diagnostics: workgroups per chunk of a 2-tile interval launch
-    if (!(value == 0 || (value >= 2 && value <= 4096)))
-      return fail(ctx, DSE_ERR_ARG, "coresident must be 0 or in 2..4096");
-    ctx->coresident = (int)value;
-  } else if (k == "dbg") {  // diagnostics bit mask: 1 one observable launch per output, 2 psi0 by
-                            // memset/copy, 4 coefficient tables on one host thread
-    ctx->dbg = (int)value;
-  } else if (k == "small") {  // registers of <= 9 qubits on the one-wave engine (dse_small.hip)
-    ctx->small = value != 0.0;
-  } else if (k == "matrix") {  // propagator-matrix mode: 0 off, 1 auto, 2 always (when eligible)
-    if (!(value == 0 || value == 1 || value == 2)) return fail(ctx, DSE_ERR_ARG, "matrix must be 0, 1 or 2");
-    ctx->matrix = (int)value;
-  } else if (k == "eig_streams") {  // dense engine: large eigendecompositions at a time (1..8)
-    if (!(value >= 1 && value <= 8)) return fail(ctx, DSE_ERR_ARG, "eig_streams must be in 1..8");
-    ctx->eig_streams = (int)value;
-  } else if (k == "eig_impl") {  // dense engine eigensolver: 0 dsyevd, 1 auto, 2 half-matrix from 2^10,
-                                 // 3 two-stage from 2^10
-    if (!(value >= 0 && value <= 3)) return fail(ctx, DSE_ERR_ARG, "eig_impl must be 0, 1, 2 or 3");
-    ctx->eig_impl = (int)value;
-  } else if (k == "eig_spin_limit") {  // two-stage eigensolver: poll rounds before a give-up (< 0: at once)
-    if (!(value >= -1 && value <= 1 << 30)) return fail(ctx, DSE_ERR_ARG, "eig_spin_limit must be in -1..2^30");
-    ctx->eig_spin = (int)value;
-  } else if (k == "dense_refine") {  // dense engine: refined eigenvalues + double-double phases
-    ctx->dense_refine = value != 0.0;
-  } else if (k == "dense_nufft") {  // dense engine: output times by the non-uniform FFT (0, 1, 2)
-    if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(ctx, DSE_ERR_ARG, "dense_nufft must be 0, 1 or 2");
-    ctx->dense_nufft = (int)value;
-  } else if (k == "symv_fused") {  // matrix mode: each product's reduction in the product's launch
-    ctx->symv_fused = value != 0.0;
-  } else if (k == "dense") {  // dense eigen-propagator engine: 0 off, 1 auto (cost model), 2 always
-    if (!(value == 0 || value == 1 || value == 2)) return fail(ctx, DSE_ERR_ARG, "dense must be 0, 1 or 2");
-    ctx->dense = (int)value;
-  } else if (k == "small_chunk") {
-    if (!(value >= 1 && value <= 1e6)) return fail(ctx, DSE_ERR_ARG, "small_chunk must be in 1..1e6");
-    ctx->small_chunk = (int)value;
   } else if (k == "handoff_fences") {  // interval kernel: agent release/acquire around each hand-off
     ctx->hk.fences = value != 0.0;
   } else if (k == "spin_limit") {  // diagnostics: partner-flag polls per hand-off (< 0: always fail)
     if (!(value >= -1 && value <= 1 << 30)) return fail(ctx, DSE_ERR_ARG, "spin_limit must be in -1..2^30");
     ctx->hk.spin_limit = (int)value;
-  } else if (k == "xcd_pairs") {
-    ctx->xcd_pairs = value != 0.0;
-  } else if (k == "span") {  // spanning registers: 0 off, 1..4 top bits (workgroups 2^s per register)
-    if (!(value >= 0 && value <= kSpanMaxTop)) return fail(ctx, DSE_ERR_ARG, "span must be in 0..4");
-    ctx->span = (int)value;
-  } else if (k == "real") {  // real-component mode for registers of 13 / 14 qubits (imaginary drives)
-    if (!(value == 0 || value == 1 || value == 2)) return fail(ctx, DSE_ERR_ARG, "real must be 0, 1 or 2");
-    ctx->real_mode = (int)value;
-  } else if (k == "span_tile") {  // spanning registers: tile bits L (0 off, -1 auto); n > L qubits span 2^(n-L) tiles
-    if (!(value == 0 || value == -1 || (value >= 10 && value <= 13)))
-      return fail(ctx, DSE_ERR_ARG, "span_tile must be -1, 0 or in 10..13");
-    ctx->span_tile = (int)value;
-  } else if (k == "span_rb") {  // amplitudes per thread of k_span: 2^span_rb (0: 512 threads)
-    if (!(value >= 0 && value <= 3)) return fail(ctx, DSE_ERR_ARG, "span_rb must be in 0..3");
-    ctx->span_rb = (int)value;
-  } else if (k == "span_partial") {  // auto span policy: span the stiffest registers beside k_interval
-    ctx->span_partial = value != 0.0;
-  } else if (k == "span_chunks") {  // auto span policy: resident launches per interval for all-span
-    if (!(value == 0.0 || value == 1.0 || value == 2.0)) return fail(ctx, DSE_ERR_ARG, "span_chunks must be 0, 1 or 2");
-    ctx->span_chunks = (int)value;
-  } else if (k == "span_partial_tile") {  // auto span policy, partial form: log2 tile (10, 11)
-    if (!(value == 10.0 || value == 11.0)) return fail(ctx, DSE_ERR_ARG, "span_partial_tile must be 10 or 11");
-    ctx->span_partial_tile = (int)value;
-  } else if (k == "mixed_launch") {
-    ctx->mixed_launch = value != 0.0;
-  } else if (k == "obs_overlap") {
-    ctx->obs_overlap = value != 0.0;
-  } else if (k == "time_kernels") {
-    if (!(value >= 0)) return fail(ctx, DSE_ERR_ARG, "time_kernels must be >= 0");
-    ctx->time_every = (int)value;
   } else if (k == "ablate" || k == "real_ablate" || k == "span_ablate") {
     // diagnostics builds only (-DDSE_DIAG): skip kernel sections (results become wrong); process-wide
     const int m = (int)value;
@@ -1913,196 +1524,6 @@ int apply_members(dse_ctx* ctx, int first, int count, hipStream_t st) {
   for (int i = 0; i < count; ++i) {
     HostProblem& P = ctx->probs[first + i];
     HIPC(launch_step(P.L, MODE_APPLY, ctx->d_probs, P.d_items, (int)P.n_tiles, 0, 0, 0, st));
-  }
-  return DSE_OK;
-}
-
-// ---- small-register engine (dse_small.hip) ------------------------------------------------
-// Problems with P.sm: Chebyshev coefficients per distinct interval length (one output per series),
-// descriptors, then every launch of the whole evolve is enqueued on the engine's own stream
-// (ceil((n_t - 1) / small_chunk) per register size); small_gather waits for them and fills obs_out.
-int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_applications,
-                 double* launches) {
-  std::vector<int> sm;
-  for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
-    if (ctx->probs[pi].sm) sm.push_back((int)pi);
-  *h_applications = 0.0;
-  *launches = 0.0;
-  if (sm.empty()) return DSE_OK;
-  if (!ctx->small_stream) HIPC(hipStreamCreateWithFlags(&ctx->small_stream, hipStreamNonBlocking));
-  // distinct interval lengths -> sets
-  std::vector<double> taus;
-  std::vector<int> iv_set(std::max(n_t - 1, 1), 0);
-  std::map<double, int> tau_id;
-  for (int m = 0; m + 1 < n_t; ++m) {
-    const double tau = t[m + 1] - t[m];
-    auto it = tau_id.find(tau);
-    if (it == tau_id.end()) {
-      if (taus.size() >= 4096) return fail(ctx, DSE_ERR_ARG, "more than 4096 distinct output intervals");
-      it = tau_id.emplace(tau, (int)taus.size()).first;
-      taus.push_back(tau);
-    }
-    iv_set[m] = it->second;
-  }
-  if (taus.empty()) taus.push_back(0.0);
-  const int n_sets = (int)taus.size();
-  std::vector<SmallProb> desc(ctx->probs.size());
-  std::memset(desc.data(), 0, desc.size() * sizeof(SmallProb));
-  Arena arena;  // every problem's coefficients and degrees, one upload
-  std::vector<std::pair<size_t, size_t>> aoff(ctx->probs.size());
-  for (int pi : sm) {
-    HostProblem& P = ctx->probs[pi];
-    const double alpha = std::max(0.5 * (P.e_max - P.e_min), 1e-300);
-    const double beta = 0.5 * (P.e_max + P.e_min);
-    std::vector<std::vector<double>> J(n_sets);
-    std::vector<int> deg(n_sets, 1);
-    int kcap = 1;
-    for (int sidx = 0; sidx < n_sets; ++sidx) {
-      const double z = alpha * taus[sidx];
-      const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
-      if (kmax > ctx->max_degree)
-        return fail(ctx, DSE_ERR_CONVERGENCE, "Chebyshev degree " + std::to_string(kmax) +
-                                                  " exceeds max_degree; use a finer output grid");
-      J[sidx].resize(kmax + 1);
-      if (dse_bessel_j(z, kmax, J[sidx].data(), tol, &deg[sidx]) != DSE_OK) return fail(ctx, DSE_ERR_ARG, "bessel failed");
-      kcap = std::max(kcap, deg[sidx]);
-    }
-    for (int m = 0; m + 1 < n_t; ++m) *h_applications += deg[iv_set[m]];
-    const int kcap1 = kcap + 1;
-    std::vector<double2> a((size_t)n_sets * kcap1, make_double2(0.0, 0.0));
-    for (int sidx = 0; sidx < n_sets; ++sidx) {
-      const double ph = -beta * taus[sidx];
-      const std::complex<double> e(std::cos(ph), std::sin(ph));
-      std::complex<double> mi(1.0, 0.0);
-      for (int k = 0; k <= deg[sidx]; ++k) {
-        const std::complex<double> v = e * mi * ((k == 0 ? 1.0 : 2.0) * J[sidx][k]);
-        a[(size_t)sidx * kcap1 + k] = make_double2(v.real(), v.imag());
-        mi *= std::complex<double>(0.0, -1.0);
-      }
-    }
-    aoff[pi].first = arena.add(a.data(), a.size() * sizeof(double2));
-    aoff[pi].second = arena.add(deg.data(), deg.size() * sizeof(int));
-    P.degree = kcap;
-    const DevProb& d = ctx->h_desc[pi];
-    SmallProb& q = desc[pi];
-    q.state = P.buf[0];
-    q.field = d.field;
-    q.zz = d.zz;
-    q.pair = nullptr;
-    q.flip = nullptr;
-    q.sea_mask = P.sea_mask;
-    q.shift = P.shift;
-    q.beta = beta;
-    q.s1 = 1.0 / alpha;
-    q.n = P.n;
-    q.rare_bit = P.rare_bit;
-    q.kcap1 = kcap1;
-    q.n_t = n_t;
-    P.final_bsel = 0;
-  }
-  {
-    int rc = upload_arena(ctx, arena, ctx->d_sm_coef, ctx->small_stream);
-    if (rc) return rc;
-  }
-  for (int pi : sm) {
-    HostProblem& P = ctx->probs[pi];
-    P.sm_coef = reinterpret_cast<double2*>(ctx->d_sm_coef.p + aoff[pi].first);
-    P.sm_deg = reinterpret_cast<int*>(ctx->d_sm_coef.p + aoff[pi].second);
-    desc[pi].coef = P.sm_coef;
-    desc[pi].deg = P.sm_deg;
-  }
-  // pair / flip tables: the problem's full n x n and 4n arrays (the device tables hold field, zz)
-  size_t extra = 0;
-  for (int pi : sm) extra += (size_t)ctx->probs[pi].n * ctx->probs[pi].n + 4 * (size_t)ctx->probs[pi].n;
-  // aux ints: per register size the selection of problems, then the interval -> set map
-  const size_t aux = ctx->probs.size() + (size_t)std::max(n_t - 1, 1) + 2 * extra + 64;
-  if (int rc = ctx->d_small_aux.reserve(ctx, aux, "small-engine allocation failed")) return rc;
-  // tables after the ints (8-byte aligned)
-  double* tab = reinterpret_cast<double*>(ctx->d_small_aux.p + ((ctx->probs.size() + std::max(n_t - 1, 1) + 1) & ~size_t(1)));
-  {
-    std::vector<double> ht;
-    ht.reserve(extra);
-    std::vector<size_t> off(ctx->probs.size(), 0);
-    for (int pi : sm) {
-      const HostProblem& P = ctx->probs[pi];
-      off[pi] = ht.size();
-      ht.insert(ht.end(), P.pair.begin(), P.pair.end());
-      // drives as the engine's kernels see them (cos(pi/2) residue dropped, build_tables)
-      for (int b = 0; b < P.n; ++b)
-        for (int c = 0; c < 4; c += 2) {
-          double re = P.flip[4 * b + c], im = P.flip[4 * b + c + 1];
-          if (std::fabs(re) <= 1e-15 * std::hypot(re, im)) re = 0.0;
-          ht.push_back(re);
-          ht.push_back(im);
-        }
-    }
-    if (!ht.empty()) HIPC(hipMemcpy(tab, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice));
-    for (int pi : sm) {
-      desc[pi].pair = tab + off[pi];
-      desc[pi].flip = tab + off[pi] + (size_t)ctx->probs[pi].n * ctx->probs[pi].n;
-    }
-  }
-  if (int rc = ctx->d_small.reserve(ctx, desc.size(), "small-engine allocation failed")) return rc;
-  HIPC(hipMemcpy(ctx->d_small.p, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
-  double* d_fam[kNumObsFamilies] = {nullptr, nullptr};  // the enabled families' outputs
-  for (ObsFamily f : kObsLaunchOrder) {
-    if (!ctx->fam[f].on) continue;
-    const size_t sn = ctx->probs.size() * (size_t)n_t * kObsFamilies[f].small_stride;
-    const std::string what = std::string("small-engine ") + kObsFamilies[f].noun + " output allocation failed";
-    if (int rc = ctx->fam[f].d_small.reserve(ctx, sn, what.c_str())) return rc;
-    d_fam[f] = ctx->fam[f].d_small.p;
-  }
-  const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
-  if (int rc = ctx->d_small_out.reserve(ctx, outn, "small-engine output allocation failed")) return rc;
-  // selections per register size, then the interval -> set map
-  std::vector<int> ints;
-  std::vector<std::pair<int, std::pair<int, int>>> groups;  // n -> (offset, count)
-  for (int n = 1; n <= kSmallMaxQubits; ++n) {
-    const int o = (int)ints.size();
-    for (int pi : sm)
-      if (ctx->probs[pi].n == n) ints.push_back(pi);
-    if ((int)ints.size() > o) groups.push_back({n, {o, (int)ints.size() - o}});
-  }
-  const int iv_off = (int)ints.size();
-  ints.insert(ints.end(), iv_set.begin(), iv_set.end());
-  HIPC(hipMemcpy(ctx->d_small_aux.p, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice));
-  hipStream_t st = ctx->small_stream;
-  for (const auto& g : groups)
-    HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
-                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
-  const int chunk = std::max(1, ctx->small_chunk);
-  for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
-    const int cnt = std::min(chunk, n_t - 1 - m0);
-    for (const auto& g : groups) {
-      HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
-      *launches += 1.0;
-    }
-  }
-  return DSE_OK;
-}
-
-int small_gather(dse_ctx* ctx, int n_t, double* obs_out) {
-  bool any = false;
-  for (auto& P : ctx->probs) any = any || P.sm;
-  if (!any) return DSE_OK;
-  HIPC(hipStreamSynchronize(ctx->small_stream));
-  std::vector<double> h(ctx->probs.size() * (size_t)n_t * 8);
-  HIPC(hipMemcpy(h.data(), ctx->d_small_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
-    const HostProblem& P = ctx->probs[pi];
-    if (!P.sm) continue;
-    for (int ti = 0; ti < n_t; ++ti)
-      finish_obs(P, h.data() + (pi * (size_t)n_t + ti) * 8, obs_out + pi * DSE_N_OBS * (size_t)n_t + ti,
-                 (size_t)n_t);
-  }
-  for (ObsFamily f : kObsReadbackOrder) {
-    if (!ctx->fam[f].on) continue;
-    const size_t S = (size_t)kObsFamilies[f].small_stride;
-    std::vector<double> hf(ctx->probs.size() * (size_t)n_t * S);
-    HIPC(hipMemcpy(hf.data(), ctx->fam[f].d_small.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t pi = 0; pi < ctx->probs.size(); ++pi)
-      if (ctx->probs[pi].sm) finish_family_outputs(ctx, f, pi, hf.data() + pi * (size_t)n_t * S, S, n_t);
   }
   return DSE_OK;
 }
@@ -2785,12 +2206,14 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   // Chebyshev coefficients of one interval dt (one set, one output)
   const double alpha = std::max(0.5 * (P.e_max - P.e_min), 1e-300);
   const double beta = 0.5 * (P.e_max + P.e_min);
-  const double z = alpha * dt;
-  const int kmax = (int)std::ceil(z + 12.0 * std::cbrt(z + 1.0) + 60.0);
-  if (kmax > ctx->max_degree) return fail(ctx, DSE_ERR_CONVERGENCE, "Chebyshev degree exceeds max_degree");
-  std::vector<double> J(kmax + 1);
-  int deg = 1;
-  if (dse_bessel_j(z, kmax, J.data(), tol, &deg) != DSE_OK) return fail(ctx, DSE_ERR_ARG, "bessel failed");
+  std::vector<std::pair<double, double>> a;
+  std::vector<double> J;
+  int deg = 1, kmax = 0;
+  {
+    const int rc = cheb_series(alpha, beta, dt, tol, ctx->max_degree, &deg, &a, &kmax, &J);
+    if (rc == DSE_ERR_CONVERGENCE) return fail(ctx, DSE_ERR_CONVERGENCE, "Chebyshev degree exceeds max_degree");
+    if (rc != DSE_OK) return fail(ctx, DSE_ERR_ARG, "bessel failed");
+  }
   // U's rotated form is symmetric when the drives are all imaginary (parity twist s_r s_c) or all
   // real: the column build runs in real arithmetic (k_ucols) and the products read the tiles on and
   // above the diagonal (k_symv); otherwise the complex column build and rocBLAS zgemv on the whole
@@ -2799,16 +2222,10 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   std::vector<double2> row(deg + 2, make_double2(0.0, 0.0));  // complex build: a_k
   std::vector<double> cf(deg + 1);                               // real build: (-1)^{k/2} c_k
   row[0] = make_double2((double)deg, 0.0);
-  {
-    const std::complex<double> e(std::cos(-beta * dt), std::sin(-beta * dt));
-    std::complex<double> mi(1.0, 0.0);
-    for (int k = 0; k <= deg; ++k) {
-      const double ck = (k == 0 ? 1.0 : 2.0) * J[k];
-      const std::complex<double> a = e * mi * ck;
-      row[1 + k] = make_double2(a.real(), a.imag());
-      cf[k] = ((k >> 1) & 1) ? -ck : ck;
-      mi *= std::complex<double>(0.0, -1.0);
-    }
+  for (int k = 0; k <= deg; ++k) {
+    const double ck = (k == 0 ? 1.0 : 2.0) * J[k];
+    row[1 + k] = make_double2(a[k].first, a[k].second);
+    cf[k] = ((k >> 1) & 1) ? -ck : ck;
   }
   // device buffers: kept in the context between calls (ctx->d_mx.p)
   const size_t nb = dim / kSymvBlock;

@@ -177,6 +177,20 @@ int main() {
         if (dse_bessel_j(z, kmax, J.data(), tol, &d) != DSE_OK) return 4;
         if (row[0].first != (double)d || row[0].second != 0.0) return 5;  // (a)
         dmax = std::max(dmax, d);
+        {  // (e) cheb_series of this tau: bit for bit the one row of cheb_rows with M = 1, and J dse_bessel_j's
+          int d1 = 0, ds = 0, over1 = 0;
+          std::vector<std::pair<double, double>> one, a;
+          std::vector<double> Js;
+          const std::vector<std::vector<double>> lone(1, std::vector<double>(1, tau));
+          if (dse::cheb_rows(alpha, beta, lone, 1, tol, 2e6, &d1, &one, &over1) != DSE_OK) return 9;
+          if (dse::cheb_series(alpha, beta, tau, tol, 2e6, &ds, &a, &over1, &Js) != DSE_OK) return 10;
+          if (ds != d || d1 != std::max(d, 1) || a.size() != (size_t)d + 1 || Js.size() != a.size()) return 11;
+          if (one.size() != (size_t)d1 + 2 || one[0].first != (double)d || one[0].second != 0.0) return 12;
+          for (int k = 0; k <= d; ++k)
+            if (!(a[k].first == one[1 + k].first && a[k].second == one[1 + k].second && Js[k] == J[k] &&
+                  a[k].first == row[1 + k].first && a[k].second == row[1 + k].second))
+              return 13;
+        }
         for (size_t k = (size_t)d + 1; k + 1 < w; ++k)  // (c)
           if (row[1 + k].first != 0.0 || row[1 + k].second != 0.0) return 6;
         for (int i = 0; i < 33; ++i) {  // (d)
@@ -214,7 +228,11 @@ def test_cheb_rows_match_bessel_and_the_propagator(tmp_path):
     exp(-i (alpha x + beta) tau) to 1e-12.  The bound: the dropped tail is below ~tol = 1e-14, and at
     most ~2,100 terms of magnitude <= 2, each coefficient rounded in fp64, sum to an error of at most
     2,100 * 2 * 2.2e-16 ~ 1e-12.  T_k by the three-term recurrence, carried with the reference phase
-    in long double, so the figure is the rows' error and not the recurrence's."""
+    in long double, so the figure is the rows' error and not the recurrence's.  cheb_series, the
+    series of one offset that cheb_rows, the small-register engine (small_launch) and the propagator-
+    matrix mode (matrix_run) are all built on, equals for every alpha and tau the row of cheb_rows with
+    M = 1 bit for bit (== on the doubles), and its J_k are dse_bessel_j's: the 1e-12 bound covers all
+    three users."""
     src = tmp_path / "rows.cpp"
     src.write_text(CHEB_ROWS_SRC)
     exe = tmp_path / "rows"
