@@ -73,7 +73,9 @@ def test_spanned_registers_match_reference_n14(engine, golden, opt):
 
 @pytest.mark.parametrize("m", [4, 3, 2, 1])
 def test_spanned_evolve_is_repeatable(engine, m):
-    """Option span_outputs = M outputs per launch (k_span staggers output j's sum to phase j % 3)."""
+    """Option span_outputs = M outputs per launch (k_span staggers output j's sum to phase j % 3).
+    Bitwise repeatability only; every M against an independent reference is in
+    test_gpu_span_cases.py::test_outputs_per_launch."""
     t = np.linspace(0.0, 2e-4, 21)
     probs = [pb.build_problem(_params(v, d, t)) for v in VARIANTS for d in DELTAS]
     runs = []
