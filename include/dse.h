@@ -45,10 +45,12 @@ extern "C" {
  * basis state (dse_set_initial_state, ...; dse_stats.custom_init_problems).
  * Later additions leave both numbers and dse_stats alone (custom_init_problems stays its last field):
  * a caller discovers them by name with dse_has_feature, and what would have been a stats counter is
- * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems). */
+ * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems; the overlaps with
+ * reference states: feature "overlap_obs", dse_overlap_problems). */
 #define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
+#define DSE_MAX_OVERLAP_REFS 16 /* reference states per problem (dse_set_overlap_refs) */
 
 enum dse_status {
   DSE_OK = 0,
@@ -408,8 +410,53 @@ int dse_pair_obs_outputs(const dse_ctx* ctx);
 /* Registers whose pair sums the last successful dse_evolve produced (a loopback partitioned register
  * counts once), 0 when there are none. */
 int dse_pair_obs_problems(const dse_ctx* ctx);
+/* ---- overlaps with stored reference states (feature "overlap_obs") ---------------------------
+ * A problem may carry K <= DSE_MAX_OVERLAP_REFS reference states phi_0 .. phi_{K-1}.  Every
+ * dse_evolve then also keeps, for every output time t_j,
+ *     o_k(t_j) = <phi_k|psi(t_j)> / ||psi(t_j)|| = sum_x conj(phi_k(x)) psi_x(t_j) / ||psi(t_j)||
+ * with psi(t_j) = exp(-i H (t_j - t_0)) psi(t_0), H including `shift`: o_k carries the true phase (the
+ * first observable of the engine that is not invariant under psi -> e^{i theta} psi).  Return
+ * amplitudes <psi(t_0)|psi(t)> (whose Fourier transform is the spectrum of the prepared state),
+ * fidelities with a target state, populations of chosen many-body states; the reference's
+ * counterpart is e_ops = [phi.proj()] of qt.sesolve (:653-666), which gives |o_k|^2 only.
+ *   - The references are used as given (not normalised: a caller may pass B psi_0).  They belong to
+ *     the problem like the initial state: kept over repeated evolves, replaced as a set, dropped by
+ *     dse_clear.  Storage: K device buffers of the state's size per register (per shard of a loopback
+ *     register its 2^n_local slice).
+ *   - With no references in the context nothing is allocated and no kernel is added; with them the
+ *     aggregates and the "site_obs" / "pair_obs" traces are bitwise what they are without, and no
+ *     engine choice (engine, lanes, chunks, outputs per launch) reads them.  Registers of one context
+ *     may hold different K, 0 included.
+ *   - Costs one more read of the state per output plus one read of each reference, and an arena of
+ *     2 K_max + 2 doubles per tile and output slot (K_max: the most references a register of the
+ *     context holds).
+ *   - dse_evolve returns DSE_ERR_ARG for a context that holds both references and a register
+ *     partitioned over processes (shard_rank >= 0).
+ *
+ * refs: [k][2^n] interleaved complex; k = 0 or refs = NULL clears.  DSE_ERR_ARG for a bad id, k above
+ * the cap, a non-finite or all-zero reference, a non-zero shard id of a loopback register (shard 0's
+ * id and whole 2^n references, as dse_set_initial_state) and a register partitioned over processes;
+ * DSE_ERR_OOM leaves the previous set in place. */
+int dse_set_overlap_refs(dse_ctx* ctx, int problem, int k, const double* refs);
+/* K of the problem (0: none), or DSE_ERR_ARG for a bad id. */
+int dse_overlap_refs(const dse_ctx* ctx, int problem);
+/* The overlaps of an arbitrary state psi (2^n interleaved complex) with the problem's references:
+ * out[2][K], Re block then Im block, divided by ||psi|| (the hook beside dse_site_observables; runs
+ * the tile kernel of the evolve; DSE_ERR_STATE for a problem without references). */
+int dse_overlaps(dse_ctx* ctx, int problem, const double* psi, double* out);
+/* After dse_evolve: out[2][K][n_t], Re block then Im block of o_k(t_j) (a loopback partitioned
+ * register: shard 0's id).  The lifetime rules of dse_get_site_obs: DSE_ERR_STATE before an evolve,
+ * for a problem without references, and after any dse_evolve that did not return DSE_OK.  After
+ * the re-run that follows a hand-off timeout the results are the re-run's (the dense engine's
+ * registers keep their first-pass results, like their aggregates). */
+int dse_get_overlaps(dse_ctx* ctx, int problem, double* out);
+/* n_t of the results dse_get_overlaps would return, 0 when there are none. */
+int dse_overlap_outputs(const dse_ctx* ctx);
+/* Registers whose overlaps the last successful dse_evolve produced (a loopback partitioned register
+ * counts once), 0 when there are none. */
+int dse_overlap_problems(const dse_ctx* ctx);
 /* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
- * "pair_obs". */
+ * "pair_obs", "overlap_obs". */
 int dse_has_feature(const char* name);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);

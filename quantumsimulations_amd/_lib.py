@@ -34,7 +34,10 @@ EXPORTED = (
     "dse_continue_from_final", "dse_get_initial_state", "dse_abi_minor",
     "dse_pair_observables", "dse_get_pair_obs", "dse_pair_obs_outputs", "dse_pair_obs_problems",
     "dse_has_feature",
+    "dse_set_overlap_refs", "dse_overlap_refs", "dse_overlaps", "dse_get_overlaps",
+    "dse_overlap_outputs", "dse_overlap_problems",
 )
+DSE_MAX_OVERLAP_REFS = 16
 DSE_DIST_ID_BYTES = 128
 DSE_XCHG_ALLTOALL, DSE_XCHG_SENDRECV, DSE_XCHG_ALLREDUCE_F64 = 1, 2, 3
 # int fn(void* user, int op, void* send, void* recv, uint64_t bytes, int peer)
@@ -121,6 +124,12 @@ def _declare(lib):
         "dse_pair_obs_outputs": (C.c_int, [_vp]),
         "dse_pair_obs_problems": (C.c_int, [_vp]),
         "dse_has_feature": (C.c_int, [C.c_char_p]),
+        "dse_set_overlap_refs": (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
+        "dse_overlap_refs": (C.c_int, [_vp, C.c_int]),
+        "dse_overlaps": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+        "dse_get_overlaps": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_overlap_outputs": (C.c_int, [_vp]),
+        "dse_overlap_problems": (C.c_int, [_vp]),
         "dse_set_initial_state": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_set_initial_product": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_continue_from_final": (C.c_int, [_vp, C.c_int]),
@@ -161,6 +170,8 @@ def lib():
             # additions after 14.1 keep both numbers (include/dse.h): they are found by name
             if not hasattr(handle, "dse_has_feature"):
                 raise ImportError("libdse.so predates dse_has_feature (two-spin correlators); rebuild it")
+            if not hasattr(handle, "dse_set_overlap_refs"):
+                raise ImportError("libdse.so predates the overlaps with reference states; rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
@@ -169,7 +180,8 @@ def lib():
 
 
 def has_feature(name: str) -> bool:
-    """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs")."""
+    """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs",
+    "overlap_obs")."""
     return bool(lib().dse_has_feature(name.encode()))
 
 

@@ -93,6 +93,14 @@ struct HostProblem {
   double2* init_state = nullptr;
   std::vector<double> init_amp;
   double* d_init_amp = nullptr;
+  // reference states of the overlaps (dse_set_overlap_refs; every shard of a loopback register
+  // alike): K device buffers of this shard's 2^n_local amplitudes and the device table of their
+  // pointers the kernels read (kMaxOverlapRefs entries).  They belong to the problem like the
+  // initial state: kept over evolves and over free_device, replaced as a set, released by dse_clear
+  // / dse_destroy
+  std::vector<double2*> ovl_refs;
+  const double2** d_ovl_tab = nullptr;
+  int ovl_k() const { return (int)ovl_refs.size(); }
 };
 
 inline int fail(dse_ctx* c, int code, const std::string& msg);
@@ -123,18 +131,20 @@ struct DevBuf {
 template <class... B>
 void release_all(B&... b) { (b.release(), ...); }
 
-// The observable families beside the seven aggregates: sums per unit (register bit, pair of bits)
-// of every output state, kept per register and read back after the evolve.  kObsFamilies below
-// describes each; the engines launch them in this order and read them back in the reverse one.
-enum ObsFamily { kSite = 0, kPair = 1, kNumObsFamilies = 2 };
-constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair};
-constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kPair, kSite};
+// The observable families beside the seven aggregates: sums per unit (register bit, pair of bits,
+// reference state) of every output state, kept per register and read back after the evolve.
+// kObsFamilies below describes each; the engines launch them in this order and read them back in the
+// reverse one.
+enum ObsFamily { kSite = 0, kPair = 1, kOverlap = 2, kNumObsFamilies = 3 };
+constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair, kOverlap};
+constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kOverlap, kPair, kSite};
 
 // What a context holds for one family: its option, a partial arena for the tile engine's kernel
 // (S doubles per tile and slot: the family's stride of the context's widest register), and the
 // results of the last evolve, per register [comps][units][n_t] (loopback group: shard 0's entry)
 struct ObsFamilyState {
-  int on = 0;
+  int on = 0;              // the option's value; kOverlap: the context holds references (set_overlap_on)
+  int kmax = 0;            // kOverlap: the most references any register of the context holds
   DevBuf<double> d_partial;
   size_t slots = 0;
   int S = 0;
@@ -384,12 +394,19 @@ struct Arena {
 };
 
 // One family: raw sums v of a register, comps per unit at v[comps * u + c] and ||psi||^2 at
-// v[comps * units], `stride` doubles per state; results normalised by that norm.
+// v[family_norm_at], `stride` doubles per state; results normalised by that norm (site, pair:
+// expectation values, sums / ||psi||^2) or by its square root (overlap: linear in psi).
+// The units of site and pair follow from the register's size; the overlap's belong to the problem
+// (its K references) and its stride to the context (K_max), so both are asked of those.
 struct ObsFamilyDesc {
   const char *option, *hook, *noun;  // the option's and the hook's names, the family's word in messages
-  int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index)
-  int (*units)(int n);
-  int (*stride)(int n);
+  int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index);
+              // overlap: Re, Im of <phi_k|psi>
+  int (*units)(const HostProblem& P);
+  int (*stride)(const dse_ctx* ctx, int n);  // of an n-qubit register of ctx
+  bool per_problem_units;  // the units are the problem's own count (0: no record) and ||psi||^2 is at
+                           // [stride - 2], where every register of the context finds it; else at [comps * units]
+  bool amplitude;   // results are sums / ||psi|| instead of sums / ||psi||^2
   int small_stride;                                        // the small engine's stride (its widest register's)
   decltype(&launch_obs_sites) launch;                      // tile engine: S >= stride(n) doubles per tile
   decltype(&launch_dense_obs_sites) launch_dense;          // dense engine, batched
@@ -404,12 +421,20 @@ struct ObsFamilyDesc {
   bool get_needs_option;  // the getter refuses once the option is back at 0 (site: serves the last record)
 };
 inline const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
-    {"site_obs", "dse_site_observables", "site", 3, [](int n) { return n; }, [](int n) { return site_stride(n); },
+    {"site_obs", "dse_site_observables", "site", 3, [](const HostProblem& P) { return P.n; },
+     [](const dse_ctx*, int n) { return site_stride(n); }, false, false,
      kSmallSiteStride, launch_obs_sites, launch_dense_obs_sites, launch_dense_obs_sites_c, &DenseProb::sites, true, false, false},
-    {"pair_obs", "dse_pair_observables", "pair", 5, [](int n) { return n * (n - 1) / 2; },
-     [](int n) { return pair_stride(n); }, kSmallPairStride, launch_obs_pairs, launch_dense_obs_pairs,
-     launch_dense_obs_pairs_c, &DenseProb::pairs, false, true, true},
+    {"pair_obs", "dse_pair_observables", "pair", 5, [](const HostProblem& P) { return P.n * (P.n - 1) / 2; },
+     [](const dse_ctx*, int n) { return pair_stride(n); }, false, false, kSmallPairStride, launch_obs_pairs,
+     launch_dense_obs_pairs, launch_dense_obs_pairs_c, &DenseProb::pairs, false, true, true},
+    // no option: on while the context holds references (dse_set_overlap_refs)
+    {"overlap references", "dse_overlaps", "overlap", 2, [](const HostProblem& P) { return P.ovl_k(); },
+     [](const dse_ctx* ctx, int) { return overlap_stride(ctx->fam[kOverlap].kmax); }, true, true, kSmallOverlapStride,
+     launch_obs_overlap, launch_dense_obs_overlap, launch_dense_obs_overlap_c, &DenseProb::ovl, false, false, true},
 };
+inline int family_norm_at(const ObsFamilyDesc& F, int units, size_t stride) {
+  return F.per_problem_units ? (int)stride - 2 : F.comps * units;
+}
 
 // ---- the functions that cross sources, by the source that defines them ---------------------------
 

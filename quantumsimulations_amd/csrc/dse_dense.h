@@ -54,6 +54,14 @@ struct DenseProb {
   // e_x0, c the row x0 of V (every kernel as it was)
   const double2* init;
   double* c;
+  // overlaps with reference states: ovl [n_t][S] raw sums (k_dense_obs_overlap), else null; the
+  // register's ovl_k references in the reference frame (dim amplitudes each); tau [n_t] the output
+  // times t_j - t_0 whose phase exp(-i shift tau_j) the columns leave out (null: columns that carry
+  // it, matrix mode's states)
+  double* ovl;
+  const double2* const* ovl_refs;
+  int ovl_k;
+  const double* tau;
 };
 
 // H' of every problem into its (zeroed) V
@@ -95,6 +103,15 @@ hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const 
                                   int tb, int t0, int S, hipStream_t st);
 hipError_t launch_dense_obs_pairs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
                                     hipStream_t st);
+// overlaps with the registers' reference states (dse_dense.hip): the raw sums of the same columns
+// into d[p].ovl rows t0 .. t0 + tb of S = overlap_stride(K_max) doubles (Re, Im of <phi_k|psi> at
+// [2 k], [2 k + 1], ||psi||^2 at [S - 2]), the frame rotation, the psi0 phase and exp(-i shift tau_j)
+// restored as launch_dense_final does for the last column; a register without references is
+// skipped; _c as above
+hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                    int tb, int t0, int S, hipStream_t st);
+hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                      hipStream_t st);
 // psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
 // the shift's phase exp(-i shift tau_last) included)
 hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,

@@ -374,6 +374,78 @@ k_dense_final(const DenseProb* __restrict__ probs, int dim, const double* __rest
   P.final_state[x] = make_double2(ph.x * ar - ph.y * ai, ph.x * ai + ph.y * ar);
 }
 
+// Overlaps of the same columns with the register's reference states (layout parameters as
+// k_dense_obs_sites, one workgroup per column): P.ovl row t0 + j holds Re, Im of <phi_k|psi(tau_j)>
+// at [2 k], [2 k + 1], ||psi||^2 at [S - 2], zero elsewhere.  The references are in the reference
+// frame and the overlap sees the global phase, so the column gets back what the engine's frame
+// leaves out, exactly as k_dense_final restores it for the last column:
+//   psi_x = exp(-i shift tau_j) i^{|x0| - |x|} psi'_x     (the powers of i when rot; x0 = 0 with a
+// custom psi(t0)); the shift's phase is the same for every x and multiplies the finished sum.
+// One pass over the column per reference (the column stays in L2), the two sums reduced over the
+// wave, then the four waves in order: no atomics.
+__global__ void __launch_bounds__(256)
+k_dense_obs_overlap(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ Psi, size_t pstride,
+                    size_t colstride, size_t imoff, int es, int t0, int S) {
+  __shared__ double red[4][2];
+  const DenseProb& P = probs[blockIdx.y];
+  const int K = P.ovl_k;
+  if (K <= 0 || !P.ovl) return;
+  const int j = blockIdx.x;
+  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
+  const double* im = re + imoff;
+  double* o = P.ovl + (size_t)(t0 + j) * S;
+  const int w = threadIdx.x >> 6;
+  double2 ph = make_double2(1.0, 0.0);
+  if (P.tau) {
+    double s, c;
+    if (P.refine)
+      dd_sincos(-P.shift, 0.0, P.tau[t0 + j], &s, &c);
+    else
+      sincos(-P.shift * P.tau[t0 + j], &s, &c);
+    ph = make_double2(c, s);
+  }
+  const int px0 = __popcll(P.x0);
+  for (int k = 0; k <= K; ++k) {  // k == K: the norm alone
+    const double2* phi = k < K ? P.ovl_refs[k] : nullptr;
+    double v[2] = {0, 0};
+    for (uint32_t x = threadIdx.x; x < (uint32_t)dim; x += 256u) {
+      double ar = re[(size_t)x * es], ai = im[(size_t)x * es];
+      if (k == K) {
+        v[0] += ar * ar + ai * ai;
+        continue;
+      }
+      if (P.rot) {
+        const double2 q = ipow(px0 - __popc(x));
+        const double t = q.x * ar - q.y * ai;
+        ai = q.x * ai + q.y * ar;
+        ar = t;
+      }
+      const double2 f = phi[x];
+      v[0] += f.x * ar + f.y * ai;  // conj(phi) psi
+      v[1] += f.x * ai - f.y * ar;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    if ((threadIdx.x & 63) == 0) red[w][0] = v[0], red[w][1] = v[1];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const double sr = red[0][0] + red[1][0] + red[2][0] + red[3][0];
+      const double si = red[0][1] + red[1][1] + red[2][1] + red[3][1];
+      if (k < K) {
+        o[2 * k] = ph.x * sr - ph.y * si;
+        o[2 * k + 1] = ph.x * si + ph.y * sr;
+      } else {
+        o[S - 2] = sr;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = 2 * K + threadIdx.x; i < S; i += 256)
+    if (i != S - 2) o[i] = 0.0;
+}
+
 }  // namespace
 
 hipError_t launch_dense_h(const DenseProb* d, int count, int dim, hipStream_t st) {
@@ -439,6 +511,20 @@ hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const 
 hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
                                     hipStream_t st) {
   hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
+                     (size_t)1, 2, t0, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                    int tb, int t0, int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_overlap, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
+                     (size_t)tb * dim, 1, t0, S);
+  return hipGetLastError();
+}
+
+hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                      hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_overlap, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
                      (size_t)1, 2, t0, S);
   return hipGetLastError();
 }

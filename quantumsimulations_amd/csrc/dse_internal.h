@@ -50,6 +50,11 @@ __host__ __device__ constexpr int site_stride(int n) { return (3 * n + 2) & ~1; 
 // (i, j), i < j, at [5 pair_index(i, j) + c] and ||psi||^2 at [5 NP], NP = n (n - 1) / 2, padded even
 __host__ __device__ constexpr int pair_index(int i, int j) { return j * (j - 1) / 2 + i; }
 __host__ __device__ constexpr int pair_stride(int n) { return (5 * (n * (n - 1) / 2) + 2) & ~1; }
+// Overlaps with stored reference states: sums per register and state, Re, Im of <phi_k|psi> at [2 k],
+// [2 k + 1] for k < K and ||psi||^2 at [S - 2], S = overlap_stride(K_max) doubles per record (K_max: the
+// most references any register of the context holds), zero elsewhere
+constexpr int kMaxOverlapRefs = 16;               // DSE_MAX_OVERLAP_REFS
+__host__ __device__ constexpr int overlap_stride(int kmax) { return 2 * kmax + 2; }
 constexpr int kMaxShardBits = 3;                  // partitioned registers: up to 8 shards
 constexpr int kMaxShards = 1 << kMaxShardBits;
 // bits above an L-bit tile for the largest register (34 qubits), at least the 32-bit tile index
@@ -139,6 +144,10 @@ struct DevProb {
   const struct RealTab* rtab;
   double* rin;
   double2* racc;
+  // overlaps with reference states (dse_overlap.hip): the register's (shard's) ovl_k references,
+  // 2^n_local amplitudes each (null, 0: none)
+  const double2* const* ovl_refs;
+  int ovl_k;
 };
 
 // ---- spanning registers (dse_span.hip): one register over 2^s cooperating workgroups ----------
@@ -316,6 +325,12 @@ hipError_t launch_obs_sites(int L, const DevProb* probs, const int2* items, int 
 hipError_t launch_obs_pairs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                             double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                             int xq = 0);
+// the overlaps with the registers' reference states of the same outputs (k_obs_overlap,
+// dse_overlap.hip): S = overlap_stride(K_max) doubles per tile, output j's partials at partial + j *
+// out_stride; the tiles of a register without references are left unwritten
+hipError_t launch_obs_overlap(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                              double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
+                              int xq = 0);
 // partial[2 * block + {0, 1}] = block sums of Re(conj(a) b) and |a|^2 over n amplitudes
 hipError_t launch_dot(const double2* a, const double2* b, size_t n, double* partial, int blocks,
                       hipStream_t st);

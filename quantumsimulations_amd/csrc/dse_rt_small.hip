@@ -76,6 +76,8 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     q.rare_bit = P.rare_bit;
     q.kcap1 = kcap1;
     q.n_t = n_t;
+    q.ovl_refs = P.d_ovl_tab;
+    q.ovl_k = P.ovl_k();
     P.final_bsel = 0;
   }
   {
@@ -122,7 +124,7 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   }
   if (int rc = ctx->d_small.reserve(ctx, desc.size(), "small-engine allocation failed")) return rc;
   HIPC(hipMemcpy(ctx->d_small.p, desc.data(), desc.size() * sizeof(SmallProb), hipMemcpyHostToDevice));
-  double* d_fam[kNumObsFamilies] = {nullptr, nullptr};  // the enabled families' outputs
+  double* d_fam[kNumObsFamilies] = {};  // the enabled families' outputs
   for (ObsFamily f : kObsLaunchOrder) {
     if (!ctx->fam[f].on) continue;
     const size_t sn = ctx->probs.size() * (size_t)n_t * kObsFamilies[f].small_stride;
@@ -147,13 +149,14 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
-                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
+                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair], d_fam[kOverlap]));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
-                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair]));
+                        cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair],
+                        d_fam[kOverlap]));
       *launches += 1.0;
     }
   }

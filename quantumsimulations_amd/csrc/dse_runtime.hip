@@ -140,6 +140,12 @@ void free_initial(HostProblem& p) {
   p.init_kind = 0;
 }
 
+void free_overlap_refs(HostProblem& p) {
+  for (double2* r : p.ovl_refs) (void)hipFree(r);
+  p.ovl_refs.clear();
+  if (p.d_ovl_tab) (void)hipFree(p.d_ovl_tab), p.d_ovl_tab = nullptr;
+}
+
 void free_device(dse_ctx* ctx) {
   for (auto& p : ctx->probs) {
     for (auto& b : p.buf)
@@ -158,7 +164,8 @@ void free_device(dse_ctx* ctx) {
   if (ctx->d_probs) (void)hipFree(ctx->d_probs), ctx->d_probs = nullptr;
   if (ctx->d_items) (void)hipFree(ctx->d_items), ctx->d_items = nullptr;
   if (ctx->d_items_iv) (void)hipFree(ctx->d_items_iv), ctx->d_items_iv = nullptr;
-  release_all(ctx->d_partial, ctx->fam[kSite], ctx->fam[kPair], ctx->d_flags, ctx->d_xslots, ctx->d_xacc, ctx->d_real,
+  for (auto& A : ctx->fam) A.release();
+  release_all(ctx->d_partial, ctx->d_flags, ctx->d_xslots, ctx->d_xacc, ctx->d_real,
               ctx->d_real_tab, ctx->d_real_items, ctx->d_span, ctx->d_span_tab, ctx->d_span_slots, ctx->d_span_flags,
               ctx->d_span_items, ctx->d_coef, ctx->d_sm_coef, ctx->d_init, ctx->d_small, ctx->d_small_out,
               ctx->d_small_aux, ctx->d_allreduce);
@@ -858,6 +865,26 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
 // ---- observable families: site-resolved observables and two-spin correlators ------------------
 
 
+// The overlap family has no option: it is on while any register of the context holds references,
+// and its stride follows the most any of them holds.  The references reach the kernels through the
+// descriptors: h_desc as dse_evolve uploads it, and with `upload` (the hook: no upload follows) the
+// device copy, every time (an evolve that failed before its upload leaves h_desc ahead of it).
+// After prepare.
+int set_overlap_on(dse_ctx* ctx, bool upload) {
+  int kmax = 0;
+  for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
+    const HostProblem& P = ctx->probs[pi];
+    kmax = std::max(kmax, P.ovl_k());
+    ctx->h_desc[pi].ovl_refs = P.d_ovl_tab;
+    ctx->h_desc[pi].ovl_k = P.ovl_k();
+  }
+  ctx->fam[kOverlap].kmax = kmax;
+  ctx->fam[kOverlap].on = kmax > 0;
+  if (upload)
+    HIPC(hipMemcpy(ctx->d_probs, ctx->h_desc.data(), ctx->h_desc.size() * sizeof(DevProb), hipMemcpyHostToDevice));
+  return DSE_OK;
+}
+
 // Refusals of the option and of the hook (`who`), decided before any work (after prepare: the tile
 // count is known): no register partitioned over processes, and with slot_cap one output slot of the
 // arena, tiles x stride(n_max) doubles, within the cap of the other arenas
@@ -867,7 +894,7 @@ int obs_family_refusal(dse_ctx* ctx, ObsFamily f, const char* who) {
     if (P.dist)
       return fail(ctx, DSE_ERR_ARG, std::string(who) + ": not available for a register partitioned over processes "
                                         "(the all-reduce of the " + F.noun + " sums is not implemented)");
-  const int S = F.stride(widest_register(ctx));
+  const int S = F.stride(ctx, widest_register(ctx));
   if (F.slot_cap && ctx->total_items * (int64_t)S * 8 > kPartialCapBytes)
     return fail(ctx, DSE_ERR_ARG, std::string(who) + ": the " + F.noun + " sums of one output (" +
                                       std::to_string(ctx->total_items) + " tiles x " + std::to_string(S) +
@@ -879,7 +906,7 @@ int obs_family_refusal(dse_ctx* ctx, ObsFamily f, const char* who) {
 // context (total_items >= 1: prepare refuses an empty context)
 int ensure_family_partial(dse_ctx* ctx, ObsFamily f, size_t slots) {
   ObsFamilyState& A = ctx->fam[f];
-  const int S = kObsFamilies[f].stride(widest_register(ctx));
+  const int S = kObsFamilies[f].stride(ctx, widest_register(ctx));
   if (A.slots >= slots && A.S == S) return DSE_OK;
   A.slots = 0;
   A.d_partial.release();
@@ -890,11 +917,11 @@ int ensure_family_partial(dse_ctx* ctx, ObsFamily f, size_t slots) {
   return DSE_OK;
 }
 
-// raw sums v of an n-qubit register, normalised into o[c][u] at o[(c * units + u) * stride]
-void finish_family(const ObsFamilyDesc& F, int n, const double* v, double* o, size_t stride) {
-  const int units = F.units(n);
-  const double n2 = v[F.comps * units];
-  const double inv = n2 > 0.0 ? 1.0 / n2 : 0.0;
+// raw sums v (a record of S doubles) of register P, normalised into o[c][u] at o[(c * units + u) * stride]
+void finish_family(const ObsFamilyDesc& F, const HostProblem& P, const double* v, size_t S, double* o, size_t stride) {
+  const int units = F.units(P);
+  const double n2 = v[family_norm_at(F, units, S)];
+  const double inv = n2 > 0.0 ? 1.0 / (F.amplitude ? std::sqrt(n2) : n2) : 0.0;
   for (int u = 0; u < units; ++u)
     for (int c = 0; c < F.comps; ++c) o[((size_t)c * units + u) * stride] = v[F.comps * u + c] * inv;
 }
@@ -903,20 +930,24 @@ void finish_family(const ObsFamilyDesc& F, int n, const double* v, double* o, si
 
 namespace dse::rt {
 // finish_family for register pi's outputs 0 .. n_t - 1, raw sums `stride` doubles apart, into its store
+// (a register without a record, an empty store: nothing)
 void finish_family_outputs(dse_ctx* ctx, ObsFamily f, size_t pi, const double* raw, size_t stride, int n_t) {
+  if (ctx->fam[f].store[pi].empty()) return;
   for (int ti = 0; ti < n_t; ++ti)
-    finish_family(kObsFamilies[f], ctx->probs[pi].n, raw + ti * stride, ctx->fam[f].store[pi].data() + ti, (size_t)n_t);
+    finish_family(kObsFamilies[f], ctx->probs[pi], raw + ti * stride, stride, ctx->fam[f].store[pi].data() + ti, (size_t)n_t);
 }
 }  // namespace dse::rt
 
 namespace {
 
 size_t obs_store_size(ObsFamily f, const HostProblem& P, int n_t) {
-  return (size_t)kObsFamilies[f].comps * kObsFamilies[f].units(P.n) * n_t;
+  return (size_t)kObsFamilies[f].comps * kObsFamilies[f].units(P) * n_t;
 }
-// which registers keep a record (a loopback group's sums live in shard 0's entry)
+// which registers keep a record (a loopback group's sums live in shard 0's entry; a family whose units
+// are the problem's own: the registers that have any)
 bool obs_record(const dse_ctx* ctx, ObsFamily f, const HostProblem& P) {
-  return ctx->fam[f].on && !(P.shard_bits > 0 && P.shard_rank != 0);
+  return ctx->fam[f].on && !(P.shard_bits > 0 && P.shard_rank != 0) &&
+         !(kObsFamilies[f].per_problem_units && kObsFamilies[f].units(P) == 0);
 }
 // registers with a record from the last evolve (0 unless it succeeded with the option on)
 int obs_family_problems(const dse_ctx* ctx, ObsFamily f) { return ctx->fam[f].nt > 0 ? ctx->fam[f].problems : 0; }
@@ -948,15 +979,17 @@ int flush_family_partials(dse_ctx* ctx, ObsFamily f, size_t nslots, size_t t0, i
     const HostProblem& P = ctx->probs[pi];
     if (P.side() || A.store[pi].empty()) continue;
     const size_t n_members = P.shard_bits > 0 ? (size_t(1) << P.shard_bits) : 1;
-    const int nv = F.comps * F.units(P.n);
+    const int nv = F.comps * F.units(P), nrm = family_norm_at(F, F.units(P), S);
     for (size_t s = 0; s < nslots; ++s) {
       std::fill(v.begin(), v.end(), 0.0);
       for (size_t mi = pi; mi < pi + n_members; ++mi) {
         const double* row = hs.data() + (s * ctx->total_items + ctx->item_pos[mi]) * S;
-        for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t)
-          for (int j = 0; j <= nv; ++j) v[j] += row[t * S + j];
+        for (int64_t t = 0; t < ctx->probs[mi].n_tiles; ++t) {
+          for (int j = 0; j < nv; ++j) v[j] += row[t * S + j];
+          v[nrm] += row[t * S + nrm];
+        }
       }
-      finish_family(F, P.n, v.data(), A.store[pi].data() + (t0 + s), (size_t)n_t);
+      finish_family(F, P, v.data(), S, A.store[pi].data() + (t0 + s), (size_t)n_t);
     }
   }
   return DSE_OK;
@@ -1247,7 +1280,7 @@ void dse_destroy(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p);
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p);
   ctx->d_mx.release();
   destroy_lanes(ctx);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
@@ -1484,7 +1517,7 @@ int dse_clear(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p);  // the initial states go with their problems
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p);  // the initial states and references go with their problems
   ctx->probs.clear();
   return DSE_OK;
 }
@@ -1619,7 +1652,7 @@ struct DenseJob {  // registers of one size, built, solved and output together
   DevArena ba;
   double *V = nullptr, *lam = nullptr, *lam_lo = nullptr, *E = nullptr, *Pm = nullptr, *Psi = nullptr, *obs = nullptr;
   double* diag_dd = nullptr;
-  double* fam[kNumObsFamilies] = {nullptr, nullptr};  // enabled families: [cnt][n_t][stride(n)] raw sums
+  double* fam[kNumObsFamilies] = {};  // enabled families: [cnt][n_t][stride(n)] raw sums
   double* c = nullptr;  // custom psi(t0): [cnt][2 dim] projected coefficients (else not allocated)
   double* tabs = nullptr;
   rocblas_int* info = nullptr;
@@ -1749,10 +1782,10 @@ int dense_alloc_job(dse_ctx* ctx, const DenseRun& R, double room, bool round_emp
   // outputs per block: P and Psi' of a problem take 2 x dim x 2 TB doubles (<= 256 MiB each)
   const int TB = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_t, (size_t(256) << 20) / (16 * dim)));
   const size_t pstride = dim * 2 * (size_t)TB;
-  size_t fS[kNumObsFamilies] = {0, 0};  // the enabled families' sums per output
+  size_t fS[kNumObsFamilies] = {}, fsum = 0;  // the enabled families' sums per output
   for (ObsFamily f : kObsLaunchOrder)
-    if (ctx->fam[f].on) fS[f] = (size_t)kObsFamilies[f].stride(n);
-  const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + fS[kSite] + fS[kPair]) + 2 * n * n + 4 * n) * sizeof(double));
+    if (ctx->fam[f].on) fsum += fS[f] = (size_t)kObsFamilies[f].stride(ctx, n);
+  const double per = (double)((dim * dim + 2 * pstride + 5 * dim + (size_t)n_t * (8 + fsum) + 2 * n * n + 4 * n) * sizeof(double));
   size_t same = 0;
   while (R.idx + same < R.order.size() && ctx->probs[R.order[R.idx + same]].n_local == n) ++same;
   size_t cnt = (size_t)std::max(0.0, room / per);
@@ -1781,7 +1814,8 @@ int dense_alloc_job(dse_ctx* ctx, const DenseRun& R, double room, bool round_emp
     J->d_desc = ba.get<DenseProb>(cnt);
   }
   ok = ok && J->V && J->lam && J->lam_lo && J->diag_dd && J->E && J->info && J->Pm && J->Psi && J->obs && J->tabs &&
-       J->d_desc && !(fS[kSite] && !J->fam[kSite]) && !(fS[kPair] && !J->fam[kPair]);
+       J->d_desc;
+  for (ObsFamily f : kObsLaunchOrder) ok = ok && !(fS[f] && !J->fam[f]);
   if (ok) return DSE_OK;
   J.reset();
   if (!round_empty) return DSE_OK;
@@ -1827,7 +1861,10 @@ int dense_fill_job(dse_ctx* ctx, const DenseRun& R, DenseJob& J) {
     D.obs = J.obs + (size_t)n_t * 8 * i;
     D.final_state = P.buf[0];
     for (ObsFamily f : kObsLaunchOrder)
-      D.*kObsFamilies[f].dense_out = J.fam[f] ? J.fam[f] + (size_t)n_t * kObsFamilies[f].stride(n) * i : nullptr;
+      D.*kObsFamilies[f].dense_out = J.fam[f] ? J.fam[f] + (size_t)n_t * kObsFamilies[f].stride(ctx, n) * i : nullptr;
+    D.ovl_refs = P.d_ovl_tab;
+    D.ovl_k = P.ovl_k();
+    D.tau = R.d_tau;
   }
   hipStream_t st = R.st;
   HIPC(hipMemcpyAsync(J.tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -1975,7 +2012,7 @@ int dense_outputs_nufft(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
     auto per_block = [&](int tb0, int tb) -> int {
       if (launch_dense_obs_c(di, (int)dim, J.Psi, tb, tb0, st) != hipSuccess) return -1;
       for (ObsFamily f : kObsLaunchOrder)
-        if (J.fam[f] && kObsFamilies[f].launch_dense_c(di, (int)dim, J.Psi, tb, tb0, kObsFamilies[f].stride(J.n), st) != hipSuccess)
+        if (J.fam[f] && kObsFamilies[f].launch_dense_c(di, (int)dim, J.Psi, tb, tb0, kObsFamilies[f].stride(ctx, J.n), st) != hipSuccess)
           return -1;
       if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, J.Psi, tb, R.tau[n_t - 1], st) != hipSuccess)
         return -1;
@@ -2012,7 +2049,7 @@ int dense_outputs_gemm(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
     HIPC(launch_dense_obs(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, st));
     for (ObsFamily f : kObsLaunchOrder)
       if (J.fam[f])
-        HIPC(kObsFamilies[f].launch_dense(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, kObsFamilies[f].stride(J.n), st));
+        HIPC(kObsFamilies[f].launch_dense(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, kObsFamilies[f].stride(ctx, J.n), st));
     if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, J.Psi, pstride, tb, R.tau[n_t - 1], st));
   }
   return DSE_OK;
@@ -2028,12 +2065,12 @@ int dense_read_back(dse_ctx* ctx, DenseRun& R, DenseJob& J, std::chrono::steady_
   std::vector<double> hf[kNumObsFamilies];
   for (ObsFamily f : kObsLaunchOrder) {
     if (!J.fam[f]) continue;
-    hf[f].resize((size_t)n_t * kObsFamilies[f].stride(J.n) * cnt);
+    hf[f].resize((size_t)n_t * kObsFamilies[f].stride(ctx, J.n) * cnt);
     HIPC(hipMemcpyAsync(hf[f].data(), J.fam[f], hf[f].size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPC(hipStreamSynchronize(st));
   for (ObsFamily f : kObsReadbackOrder) {
-    const size_t S = (size_t)kObsFamilies[f].stride(J.n);
+    const size_t S = (size_t)kObsFamilies[f].stride(ctx, J.n);
     for (int i = 0; i < cnt && J.fam[f]; ++i)
       finish_family_outputs(ctx, f, (size_t)J.list[i], hf[f].data() + (size_t)i * n_t * S, S, n_t);
   }
@@ -2243,9 +2280,9 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
                oCnt = take(nb * sizeof(int));
   // the enabled observable families: their sums of the same states, kept with the mode's other buffers
   // (taken last and only with the option on: every other offset, and the size with it off, as before)
-  size_t oFam[kNumObsFamilies] = {0, 0};
+  size_t oFam[kNumObsFamilies] = {};
   for (ObsFamily f : kObsLaunchOrder)
-    if (ctx->fam[f].on) oFam[f] = take((size_t)n_t * kObsFamilies[f].stride(n) * sizeof(double));
+    if (ctx->fam[f].on) oFam[f] = take((size_t)n_t * kObsFamilies[f].stride(ctx, n) * sizeof(double));
   if (int rc = ctx->d_mx.reserve(ctx, off, "propagator-matrix mode: allocation failed")) return rc;
   unsigned char* base = ctx->d_mx.p;
   double2* U = reinterpret_cast<double2*>(base + oU);     // tiles (real build) or columns: U e_c
@@ -2356,14 +2393,16 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.obs = d_obs;
   for (ObsFamily f : kObsLaunchOrder)
     if (ctx->fam[f].on) D.*kObsFamilies[f].dense_out = reinterpret_cast<double*>(base + oFam[f]);
+  D.ovl_refs = P.d_ovl_tab;  // (tau null: the states are in the computational frame, the shift's phase in U)
+  D.ovl_k = P.ovl_k();
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
   std::vector<double> hfam[kNumObsFamilies];
   for (ObsFamily f : kObsLaunchOrder) {
     if (!ctx->fam[f].on) continue;
     const ObsFamilyDesc& F = kObsFamilies[f];
-    hfam[f].resize((size_t)n_t * F.stride(n));
-    HIPC(F.launch_dense_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, F.stride(n), st));
+    hfam[f].resize((size_t)n_t * F.stride(ctx, n));
+    HIPC(F.launch_dense_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, F.stride(ctx, n), st));
     HIPC(hipMemcpyAsync(hfam[f].data(), D.*F.dense_out, hfam[f].size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPC(hipMemcpyAsync(P.buf[0], S + dim * (size_t)(n_t - 1), dim * sizeof(double2), hipMemcpyDeviceToDevice, st));
@@ -2376,7 +2415,7 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   for (int ti = 0; ti < n_t; ++ti)
     finish_obs(P, h.data() + (size_t)ti * 8, obs_out + (size_t)pi * DSE_N_OBS * n_t + ti, (size_t)n_t);
   for (ObsFamily f : kObsLaunchOrder)
-    if (ctx->fam[f].on) finish_family_outputs(ctx, f, (size_t)pi, hfam[f].data(), (size_t)kObsFamilies[f].stride(n), n_t);
+    if (ctx->fam[f].on) finish_family_outputs(ctx, f, (size_t)pi, hfam[f].data(), (size_t)kObsFamilies[f].stride(ctx, n), n_t);
   P.degree = deg;
   *h_apps = (double)deg * (double)dim;
   float b_ms = 0.f, p_ms = 0.f;
@@ -2418,8 +2457,10 @@ int obs_family_hook(dse_ctx* ctx, ObsFamily f, int problem, const double* psi, d
   if (F.hook_refuses_shard_early && ctx->probs[first].dist)
     return fail(ctx, DSE_ERR_ARG, std::string(F.hook) + ": not available for a dist shard");
   HIPC(hipSetDevice(ctx->device));
-  if ((rc = prepare(ctx))) return rc;
+  if ((rc = prepare(ctx)) || (rc = set_overlap_on(ctx, true))) return rc;
   if (!F.hook_refuses_shard_early && (rc = obs_family_refusal(ctx, f, F.hook))) return rc;
+  if (F.per_problem_units && F.units(ctx->probs[first]) == 0)
+    return fail(ctx, DSE_ERR_STATE, std::string(F.hook) + ": the problem has no " + F.option);
   const int64_t tiles = member_tiles(ctx, first, count);
   if ((rc = ensure_family_partial(ctx, f, 1))) return rc;
   const size_t S = (size_t)ctx->fam[f].S;
@@ -2435,12 +2476,14 @@ int obs_family_hook(dse_ctx* ctx, ObsFamily f, int problem, const double* psi, d
   std::vector<double> h(tiles * S);
   HIPC(hipMemcpyAsync(h.data(), d_partial, h.size() * sizeof(double), hipMemcpyDeviceToHost, st));
   HIPC(hipStreamSynchronize(st));
-  const int n = ctx->probs[first].n;
-  const int nv = F.comps * F.units(n);
+  const int units = F.units(ctx->probs[first]);
+  const int nv = F.comps * units, nrm = family_norm_at(F, units, S);
   std::vector<double> v(S, 0.0);
-  for (int64_t t = 0; t < tiles; ++t)
-    for (int j = 0; j <= nv; ++j) v[j] += h[t * S + j];
-  finish_family(F, n, v.data(), out, 1);
+  for (int64_t t = 0; t < tiles; ++t) {
+    for (int j = 0; j < nv; ++j) v[j] += h[t * S + j];
+    v[nrm] += h[t * S + nrm];
+  }
+  finish_family(F, ctx->probs[first], v.data(), S, out, 1);
   ctx->evolved = false;
   return DSE_OK;
 }
@@ -2454,10 +2497,14 @@ int obs_family_get(dse_ctx* ctx, ObsFamily f, int problem, double* out) {
   int rc = hook_members(ctx, problem, &first, &count);
   if (rc) return rc;
   const ObsFamilyState& A = ctx->fam[f];
-  if (A.nt <= 0 || (size_t)problem >= A.store.size() || (kObsFamilies[f].get_needs_option && !A.on) ||
+  const bool no_units = kObsFamilies[f].per_problem_units && kObsFamilies[f].units(ctx->probs[problem]) == 0;
+  if (A.nt <= 0 || (size_t)problem >= A.store.size() || (kObsFamilies[f].get_needs_option && !A.on) || no_units ||
       A.store[problem].size() != obs_store_size(f, ctx->probs[problem], A.nt))
-    return fail(ctx, DSE_ERR_STATE, std::string("no ") + kObsFamilies[f].noun + " observables (set option " +
-                                        kObsFamilies[f].option + " = 1 and call dse_evolve first)");
+    return fail(ctx, DSE_ERR_STATE, std::string("no ") + kObsFamilies[f].noun + " observables (" +
+                                        (kObsFamilies[f].per_problem_units
+                                             ? std::string("give the problem ") + kObsFamilies[f].option
+                                             : std::string("set option ") + kObsFamilies[f].option + " = 1") +
+                                        " and call dse_evolve first)");
   std::copy(A.store[problem].begin(), A.store[problem].end(), out);
   return DSE_OK;
 }
@@ -2528,10 +2575,15 @@ int dse_pair_obs_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kPair].nt :
 int dse_pair_obs_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kPair) : DSE_ERR_ARG; }
 int dse_get_pair_obs(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kPair, problem, out); }
 
+int dse_overlaps(dse_ctx* ctx, int problem, const double* psi, double* out) { return obs_family_hook(ctx, kOverlap, problem, psi, out); }
+int dse_overlap_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kOverlap].nt : DSE_ERR_ARG; }
+int dse_overlap_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kOverlap) : DSE_ERR_ARG; }
+int dse_get_overlaps(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kOverlap, problem, out); }
+
 int dse_has_feature(const char* name) {
   if (!name) return 0;
   const std::string k(name);
-  return k == "site_obs" || k == "initial_state" || k == "pair_obs";
+  return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs";
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -3547,7 +3599,7 @@ int size_obs_chunks(dse_ctx* ctx, EvolvePlan& pl) {
   pl.chunk = partial_chunk(tiles * 64, pl.M, pl.n_t);
   for (ObsFamily f : kObsLaunchOrder)
     if (ctx->fam[f].on)
-      pl.chunk = std::min(pl.chunk, partial_chunk(tiles * kObsFamilies[f].stride(n_max) * 8, pl.M, pl.n_t));
+      pl.chunk = std::min(pl.chunk, partial_chunk(tiles * kObsFamilies[f].stride(ctx, n_max) * 8, pl.M, pl.n_t));
   for (ObsFamily f : kObsLaunchOrder)
     if (ctx->fam[f].on && (rc = ensure_family_partial(ctx, f, pl.chunk))) return rc;
   if ((rc = ensure_partial(ctx, pl.chunk))) return rc;
@@ -3859,7 +3911,7 @@ int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_
   ctx->xms = 0.0;
   ctx->xev_used = 0;
   pl.phase("prepare");
-  if ((rc = choose_engines(ctx, pl))) return rc;
+  if ((rc = set_overlap_on(ctx, false)) || (rc = choose_engines(ctx, pl))) return rc;
   choose_span(ctx, pl);
   choose_real(ctx, pl);
   if ((rc = choose_wht(ctx, pl))) return rc;
@@ -4011,6 +4063,76 @@ int dse_set_initial_state(dse_ctx* ctx, int problem, const double* psi) {
   }
   set_init_stored(ctx, first, count);
   return DSE_OK;
+}
+
+int dse_set_overlap_refs(dse_ctx* ctx, int problem, int k, const double* refs) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_overlap_refs");
+  if (rc) return rc;
+  if (k < 0 || k > DSE_MAX_OVERLAP_REFS)
+    return fail(ctx, DSE_ERR_ARG, "dse_set_overlap_refs: k must be in 0.." + std::to_string(DSE_MAX_OVERLAP_REFS));
+  HIPC(hipSetDevice(ctx->device));
+  if (k == 0 || !refs) {
+    (void)sync_all(ctx);
+    for (int i = 0; i < count; ++i) free_overlap_refs(ctx->probs[first + i]);
+    return DSE_OK;
+  }
+  const size_t total = size_t(1) << ctx->probs[first].n;
+  for (int r = 0; r < k; ++r) {
+    bool nonzero = false;
+    for (size_t i = 0; i < 2 * total; ++i) {
+      const double a = refs[2 * total * r + i];
+      if (!std::isfinite(a)) return fail(ctx, DSE_ERR_ARG, "dse_set_overlap_refs: non-finite amplitude");
+      nonzero = nonzero || a != 0.0;
+    }
+    if (!nonzero) return fail(ctx, DSE_ERR_ARG, "dse_set_overlap_refs: reference " + std::to_string(r) + " is zero");
+  }
+  // the new set beside the old one: a failed allocation leaves the previous set in place
+  std::vector<std::vector<double2*>> fresh(count);
+  std::vector<const double2**> tabs(count, nullptr);
+  bool ok = true;
+  for (int i = 0; i < count && ok; ++i) {
+    const size_t amps = size_t(1) << ctx->probs[first + i].n_local;
+    for (int r = 0; r < k && ok; ++r) {
+      double2* b = nullptr;
+      ok = hipMalloc(&b, amps * sizeof(double2)) == hipSuccess;
+      if (ok) fresh[i].push_back(b);
+    }
+    ok = ok && hipMalloc(&tabs[i], kMaxOverlapRefs * sizeof(double2*)) == hipSuccess;
+  }
+  const double2* in = reinterpret_cast<const double2*>(refs);
+  hipError_t he = hipSuccess;
+  for (int i = 0; i < count && ok && he == hipSuccess; ++i) {
+    const size_t amps = size_t(1) << ctx->probs[first + i].n_local;
+    for (int r = 0; r < k && he == hipSuccess; ++r)
+      he = hipMemcpy(fresh[i][r], in + total * r + i * amps, amps * sizeof(double2), hipMemcpyHostToDevice);
+    std::vector<const double2*> tab(kMaxOverlapRefs, nullptr);
+    std::copy(fresh[i].begin(), fresh[i].end(), tab.begin());
+    if (he == hipSuccess) he = hipMemcpy(tabs[i], tab.data(), tab.size() * sizeof(double2*), hipMemcpyHostToDevice);
+  }
+  if (!ok || he != hipSuccess) {
+    (void)hipGetLastError();
+    for (int i = 0; i < count; ++i) {
+      for (double2* b : fresh[i]) (void)hipFree(b);
+      if (tabs[i]) (void)hipFree(tabs[i]);
+    }
+    if (!ok) return fail(ctx, DSE_ERR_OOM, "overlap reference buffer allocation failed");
+    return fail(ctx, DSE_ERR_HIP, std::string("dse_set_overlap_refs: ") + hipGetErrorString(he));
+  }
+  (void)sync_all(ctx);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    free_overlap_refs(P);
+    P.ovl_refs = fresh[i];
+    P.d_ovl_tab = tabs[i];
+  }
+  return DSE_OK;
+}
+
+int dse_overlap_refs(const dse_ctx* ctx, int problem) {
+  if (!ctx || problem < 0 || problem >= (int)ctx->probs.size()) return DSE_ERR_ARG;
+  return ctx->probs[problem].ovl_k();
 }
 
 int dse_set_initial_product(dse_ctx* ctx, int problem, const double* amp) {

@@ -15,6 +15,9 @@ constexpr int kSmallSiteStride = 28;
 // two-spin sums per problem and output (option pair_obs): ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at
 // [5 p + c], ||psi||^2 at [5 NP], padded to an even count for n = 9 (pair_stride(9))
 constexpr int kSmallPairStride = 182;
+// overlaps with reference states per problem and output: Re, Im of <phi_k|psi> at [2 k], [2 k + 1],
+// ||psi||^2 at [32] (overlap_stride(16): every register's record is sized for the cap)
+constexpr int kSmallOverlapStride = 2 * 16 + 2;
 
 struct SmallProb {
   double2* state;          // [2^n] the state at the start of the next launch
@@ -27,17 +30,23 @@ struct SmallProb {
   uint64_t sea_mask;
   double shift, beta, s1;
   int n, rare_bit, kcap1, n_t;
+  // the register's ovl_k reference states, 2^n amplitudes each (null, 0: none)
+  const double2* const* ovl_refs;
+  int ovl_k;
 };
 
 // One launch: intervals m0 .. m0 + n_int - 1 of problems sel[0 .. count) (all with n qubits);
 // out[problem][m + 1][8] = raw observable sums of psi(t_{m+1}) (dse_runtime.hip finish_obs).
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
                         const int* iv_set, double* out, hipStream_t st, double* sites = nullptr,
-                        double* pairs = nullptr);
+                        double* pairs = nullptr, double* ovl = nullptr);
 // out[problem][0][8] = observable sums of the state buffer (psi0)
 // sites non-null (both launches): also sites[problem][m][kSmallSiteStride], the site-resolved sums
 // pairs non-null (both launches): also pairs[problem][m][kSmallPairStride], the two-spin sums
+// ovl non-null (both launches): also ovl[problem][m][kSmallOverlapStride], the overlaps with the
+// problem's reference states (a problem without references: its records are left unwritten)
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites = nullptr, double* pairs = nullptr);
+                             hipStream_t st, double* sites = nullptr, double* pairs = nullptr,
+                             double* ovl = nullptr);
 
 }  // namespace dse

@@ -118,261 +118,79 @@ __device__ __forceinline__ void small_pair_sums(const double2* w, int lane, bool
     }
 }
 
-// SITES: also the site-resolved sums of every output into sites[problem][m][kSmallSiteStride]
-// (the 7 aggregate sums keep their code and order); PAIRS: after them the two-spin sums into
-// pairs[problem][m][kSmallPairStride]
-template <int N, bool SITES, bool PAIRS>
-__global__ void __launch_bounds__(64)
-k_small(const SmallProb* __restrict__ probs, const int* __restrict__ sel, int m0, int n_int,
-        const int* __restrict__ iv_set, double* __restrict__ out, double* __restrict__ sites,
-        double* __restrict__ pairs) {
-  using G = SmallGeo<N>;
-  constexpr int R = G::R, DIM = G::DIM, NP = G::NP;
-  __shared__ double2 w[DIM];
-  __shared__ double2 fl[N][2];  // drive coefficient of bit b for output bit value v
-  __shared__ double pg[NP > 0 ? NP : 1];
-  __shared__ int pm[NP > 0 ? NP : 1];   // pair masks e_i | e_j
-  __shared__ double red[8];
-
-  const SmallProb& P = probs[sel[blockIdx.x]];
-  const int lane = threadIdx.x;
-  const bool live = lane < DIM;
-  const gd2* gst_ = gptr((const double2*)P.state);
-
-  // tables -> LDS; the diagonal D(x) - beta of the owned amplitudes -> registers
-  if (lane < N) {
-    fl[lane][0] = make_double2(P.flip[4 * lane + 0], P.flip[4 * lane + 1]);
-    fl[lane][1] = make_double2(P.flip[4 * lane + 2], P.flip[4 * lane + 3]);
-  }
-  for (int e = lane; e < NP; e += 64) {
-    int i = 0, rem = e;
-    while (rem >= N - 1 - i) rem -= N - 1 - i, ++i;
-    pg[e] = P.pair[i * N + i + 1 + rem];
-    pm[e] = (1 << i) | (1 << (i + 1 + rem));
-  }
-  double dmb[R];
+// Overlaps of the state in LDS w with the problem's K reference states (the record of
+// dse_overlap.hip at the stride kSmallOverlapStride): the wave reads each reference from memory (2^N
+// x 16 B <= 8 KiB, 16-byte loads) and dots it with the state, one wave butterfly per sum, references
+// in order.  K = 0: nothing is written.
+template <int N>
+__device__ __forceinline__ void small_overlap_sums(const double2* w, int lane, bool live,
+                                                   const double2* const* refs, int K, double* o) {
+  constexpr int R = SmallGeo<N>::R;
+  if (K <= 0) return;
+  double n2 = 0.0;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    const int x = r * 64 + lane;
-    double d = P.shift - P.beta;
-    for (int b = 0; b < N; ++b) {
-      const double sb = 0.5 - (double)((x >> b) & 1);
-      d += P.field[b] * sb;
-      for (int c = b + 1; c < N; ++c) d += P.zz[b * N + c] * (sb * (0.5 - (double)((x >> c) & 1)));
-    }
-    dmb[r] = d;
-    if (!PAIRS && live) w[x] = gld(gst_, x);  // (the instances without pair sums: their code as it was)
+    const double2 p = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
+    n2 += p.x * p.x + p.y * p.y;
   }
-  if (PAIRS) {
-    // The state in a loop of its own.  Stored to LDS inside the loop above, each store might alias the
-    // coefficient tables read through generic pointers, so all R x N (N + 1) / 2 loads are issued again
-    // per row: at N = 9 that prologue spilled (246 VGPRs, 988 B of scratch per lane).
 #pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (live) w[r * 64 + lane] = gld(gst_, r * 64 + lane);
-  }
-  __syncthreads();
-
-  const double s1 = P.s1, inv2s1 = 0.5 / s1;
-  for (int mi = 0; mi < n_int; ++mi) {
-    const int m = m0 + mi;  // interval [t_m, t_{m+1}]
-    const int set = iv_set[m];
-    const cptr<double> a = (cptr<double>)(P.coef + (size_t)set * P.kcap1);  // a_k = (a[2k], a[2k+1])
-    const int K = P.deg[set];
-    double2 o[R], acc[R];
-    {
-      const double2 a0 = make_double2(a[0], a[1]);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const double2 v = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
-        acc[r] = cmad(make_double2(0.0, 0.0), a0.x, a0.y, v);
-        o[r] = make_double2(0.0, 0.0);
-      }
-    }
-    for (int k = 1; k <= K; ++k) {
-      double2 own[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int x = r * 64 + lane;
-        own[r] = live ? w[x] : make_double2(0.0, 0.0);
-        o[r].x = fma(dmb[r], own[r].x, o[r].x);
-        o[r].y = fma(dmb[r], own[r].y, o[r].y);
-      }
-#pragma unroll
-      for (int b = 0; b < N; ++b) {
-        const double2 c0 = fl[b][0], c1 = fl[b][1];
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const int x = r * 64 + lane;
-          if (!live) continue;
-          const double2 c = ((x >> b) & 1) ? c1 : c0;
-          o[r] = cmad(o[r], c.x, c.y, w[x ^ (1 << b)]);
-        }
-      }
-      if (N <= 7) {  // every pair's mask at compile time
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < N; ++i)
-#pragma unroll
-          for (int j = i + 1; j < N; ++j, ++e) {
-            const double g = pg[e];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-              const int x = r * 64 + lane;
-              if (!live || (((x >> i) ^ (x >> j)) & 1)) continue;
-              const double2 v = w[x ^ ((1 << i) | (1 << j))];
-              o[r].x = fma(g, v.x, o[r].x);
-              o[r].y = fma(g, v.y, o[r].y);
-            }
-          }
-      } else {  // 28 / 36 pairs: a loop (an unrolled one hoists every coefficient into registers)
+  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+  if (2 * K + lane < kSmallOverlapStride) o[2 * K + lane] = (2 * K + lane == kSmallOverlapStride - 2) ? n2 : 0.0;
 #pragma unroll 1
-        for (int e = 0; e < NP; ++e) {
-          const double g = pg[e];
-          const int m = pm[e];
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const int x = r * 64 + lane;
-            if (!live || (__popc(x & m) & 1)) continue;
-            const double2 v = w[x ^ m];
-            o[r].x = fma(g, v.x, o[r].x);
-            o[r].y = fma(g, v.y, o[r].y);
-          }
-        }
-      }
-      const double sc = (k == 1) ? s1 : 2.0 * s1;
-      const double2 ak = make_double2(a[2 * k], a[2 * k + 1]);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        o[r].x *= sc;
-        o[r].y *= sc;
-        acc[r] = cmad(acc[r], ak.x, ak.y, o[r]);
-      }
-      __syncthreads();  // all reads of w_{k-1} done
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int x = r * 64 + lane;
-        if (live) w[x] = o[r];
-        o[r] = make_double2(-inv2s1 * own[r].x, -inv2s1 * own[r].y);  // the next term's -w_{k-2}/(2 s1)
-      }
-      __syncthreads();
-    }
-    // psi(t_{m+1}) = acc -> LDS (w_0 of the next interval), then its observables
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-      if (live) w[r * 64 + lane] = acc[r];
-    __syncthreads();
-    double v[7] = {0, 0, 0, 0, 0, 0, 0};
-    if (live) {
-      const double half_sea = 0.5 * (double)__popcll(P.sea_mask);
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int x = r * 64 + lane;
-        const double2 p = acc[r];
-        const double p2 = p.x * p.x + p.y * p.y;
-        v[6] += p2;
-        v[2] += p2 * (half_sea - (double)__popcll((uint64_t)x & P.sea_mask));
-        if (P.rare_bit >= 0) v[3] += p2 * (0.5 - (double)((x >> P.rare_bit) & 1));
-#pragma unroll
-        for (int b = 0; b < N; ++b) {
-          const bool sea = (P.sea_mask >> b) & 1ull, rr = (b == P.rare_bit);
-          if ((!sea && !rr) || ((x >> b) & 1)) continue;
-          const double2 s = w[x ^ (1 << b)];
-          const double re = p.x * s.x + p.y * s.y, im = p.x * s.y - p.y * s.x;
-          if (sea) v[0] += re, v[1] += im;
-          if (rr) v[4] += re, v[5] += im;
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      double t = v[j];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-      if (lane == 0) red[j] = t;
-    }
-    __syncthreads();
-    if (lane < 8) out[((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * 8 + lane] = lane < 7 ? red[lane] : 0.0;
-    if (SITES)
-      small_site_sums<N>(w, lane, live, sites + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallSiteStride);
-    if (PAIRS)
-      small_pair_sums<N>(w, lane, live, pairs + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallPairStride);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    if (live) gst(gptr((double2*)P.state), r * 64 + lane, w[r * 64 + lane]);
-}
-
-// observables of the initial state (output 0)
-template <int N, bool SITES, bool PAIRS>
-__global__ void __launch_bounds__(64)
-k_small_obs0(const SmallProb* __restrict__ probs, const int* __restrict__ sel, double* __restrict__ out,
-             double* __restrict__ sites, double* __restrict__ pairs) {
-  using G = SmallGeo<N>;
-  constexpr int R = G::R, DIM = G::DIM;
-  __shared__ double2 w[DIM];
-  const SmallProb& P = probs[sel[blockIdx.x]];
-  const int lane = threadIdx.x;
-  const bool live = lane < DIM;
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-    if (live) w[r * 64 + lane] = gld(gptr((const double2*)P.state), r * 64 + lane);
-  __syncthreads();
-  double v[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (live) {
-    const double half_sea = 0.5 * (double)__popcll(P.sea_mask);
+  for (int k = 0; k < K; ++k) {
+    const gd2* gref = gptr(refs[k]);
+    double re = 0.0, im = 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const int x = r * 64 + lane;
-      const double2 p = w[x];
-      const double p2 = p.x * p.x + p.y * p.y;
-      v[6] += p2;
-      v[2] += p2 * (half_sea - (double)__popcll((uint64_t)x & P.sea_mask));
-      if (P.rare_bit >= 0) v[3] += p2 * (0.5 - (double)((x >> P.rare_bit) & 1));
-      for (int b = 0; b < N; ++b) {
-        const bool sea = (P.sea_mask >> b) & 1ull, rr = (b == P.rare_bit);
-        if ((!sea && !rr) || ((x >> b) & 1)) continue;
-        const double2 s = w[x ^ (1 << b)];
-        const double re = p.x * s.x + p.y * s.y, im = p.x * s.y - p.y * s.x;
-        if (sea) v[0] += re, v[1] += im;
-        if (rr) v[4] += re, v[5] += im;
-      }
+      if (!live) continue;
+      const double2 f = gld(gref, r * 64 + lane);
+      const double2 p = w[r * 64 + lane];
+      re += f.x * p.x + f.y * p.y;  // conj(phi) psi
+      im += f.x * p.y - f.y * p.x;
     }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      re += __shfl_xor(re, off, 64);
+      im += __shfl_xor(im, off, 64);
+    }
+    if (lane < 2) o[2 * k + lane] = lane == 0 ? re : im;
   }
-  for (int j = 0; j < 7; ++j) {
-    double t = v[j];
-    for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off, 64);
-    v[j] = t;
-  }
-  if (lane == 0) {
-    double* o = out + (size_t)sel[blockIdx.x] * P.n_t * 8;
-    for (int j = 0; j < 7; ++j) o[j] = v[j];
-    o[7] = 0.0;
-  }
-  if (SITES) small_site_sums<N>(w, lane, live, sites + (size_t)sel[blockIdx.x] * P.n_t * kSmallSiteStride);
-  if (PAIRS) small_pair_sums<N>(w, lane, live, pairs + (size_t)sel[blockIdx.x] * P.n_t * kSmallPairStride);
 }
+
+#define DSE_SMALL_OVL 0
+#include "dse_small_kernels.inc"
+#undef DSE_SMALL_OVL
+#define DSE_SMALL_OVL 1
+#include "dse_small_kernels.inc"
+#undef DSE_SMALL_OVL
 
 }  // namespace
 
 #define DSE_SMALL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
 
-// (SITES, PAIRS) of a launch from the two output pointers
-#define DSE_SMALL_VARIANT(K, q, ...)                                                              \
-  do {                                                                                            \
-    if (sites && pairs)                                                                           \
-      hipLaunchKernelGGL((K<q, true, true>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);   \
-    else if (pairs)                                                                               \
-      hipLaunchKernelGGL((K<q, false, true>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);  \
-    else if (sites)                                                                               \
-      hipLaunchKernelGGL((K<q, true, false>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);  \
-    else                                                                                          \
-      hipLaunchKernelGGL((K<q, false, false>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs); \
+// (SITES, PAIRS) of a launch from the two output pointers; with ovl the _ovl kernel of the same two
+#define DSE_SMALL_LAUNCH(K, q, S_, P_, ...)                                                                  \
+  do {                                                                                                       \
+    if (ovl)                                                                                                 \
+      hipLaunchKernelGGL((K##_ovl<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl); \
+    else                                                                                                     \
+      hipLaunchKernelGGL((K<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);           \
+  } while (0)
+#define DSE_SMALL_VARIANT(K, q, ...)                     \
+  do {                                                   \
+    if (sites && pairs)                                  \
+      DSE_SMALL_LAUNCH(K, q, true, true, __VA_ARGS__);   \
+    else if (pairs)                                      \
+      DSE_SMALL_LAUNCH(K, q, false, true, __VA_ARGS__);  \
+    else if (sites)                                      \
+      DSE_SMALL_LAUNCH(K, q, true, false, __VA_ARGS__);  \
+    else                                                 \
+      DSE_SMALL_LAUNCH(K, q, false, false, __VA_ARGS__); \
   } while (0)
 
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
-                        const int* iv_set, double* out, hipStream_t st, double* sites, double* pairs) {
+                        const int* iv_set, double* out, hipStream_t st, double* sites, double* pairs,
+                        double* ovl) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
@@ -386,7 +204,7 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 }
 
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites, double* pairs) {
+                             hipStream_t st, double* sites, double* pairs, double* ovl) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \

@@ -40,7 +40,7 @@ __all__ = [
     "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch", "simulate_rare_sites",
     "simulate_rare_pairs",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
-    "simulate_rare_from", "simulate_rare_sequence",
+    "simulate_rare_from", "simulate_rare_sequence", "simulate_rare_overlaps",
 ]
 
 _ENGINES: Dict[int, object] = {}
@@ -327,9 +327,12 @@ def _check_start(psi0, spins) -> None:
         raise ValueError("pass exactly one of psi0 and spins")
 
 
-def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site):
+def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng=None):
     """One evolve of the unreduced register of ``params`` from an engine-order ket or a product
-    state; returns (t, obs dict, final state in engine order, the Problem)."""
+    state; returns (t, obs dict, final state in engine order, the Problem).  ``refs_eng``: reference
+    states of the register in engine order, (K, 2^n), or "initial" (the state the evolve starts
+    from, as the engine holds it); the overlap traces (K, n_t) are then returned as a fifth item.
+    The engine is left cleared, so without references."""
     t = time_grid(params)
     prob = build_problem(params, order="engine", reduce=False)
     eng.clear()
@@ -339,11 +342,15 @@ def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site):
             eng.set_initial_state(pid, psi_eng)
         else:
             eng.set_initial_product(pid, amps_by_site[prob.site_of_bit])
+        if refs_eng is not None:
+            eng.set_overlap_refs(pid, eng.initial_state(pid)[None, :] if isinstance(refs_eng, str) else refs_eng)
         obs, _ = eng.evolve(t, tol=_tol())
         final = eng.state(pid)
+        ovl = eng.overlap_traces(pid) if refs_eng is not None else None
     finally:
         eng.clear()
-    return t, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}, final, prob
+    out = (t, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}, final, prob)
+    return out if refs_eng is None else out + (ovl,)
 
 
 def simulate_rare_from(params: DipolarRareParams, psi0=None, spins=None, return_state: bool = False,
@@ -367,6 +374,39 @@ def simulate_rare_from(params: DipolarRareParams, psi0=None, spins=None, return_
     if return_state:
         return t, obs, engine_to_reference_state(final, prob.site_of_bit)
     return t, obs
+
+
+def simulate_rare_overlaps(params: DipolarRareParams, refs, psi0=None, spins=None, device: int | None = None):
+    """simulate_rare_from that also returns the overlaps with reference states:
+    ``(t, obs, overlaps)``, ``overlaps[k, j] = <refs[k]|psi(t_j)> / ||psi(t_j)||`` (complex128, with
+    the phase of psi(t) = exp(-i H (t - t_0)) psi(t_0)).
+
+    ``refs``: a ``(K, 2^(n_sea + 1))`` array of kets in the reference's basis order (used as given,
+    not normalised; K <= 16), or the string ``"initial"``: K = 1, the initial state itself, i.e. the
+    return amplitude <psi(t_0)|psi(t)> whose Fourier transform is the spectrum of the prepared
+    state.  ``psi0`` / ``spins`` as in simulate_rare_from (at most one); with neither the evolution
+    starts from ``initial_state_rare(params)``.  ``obs`` is what simulate_rare_from returns for the
+    same start."""
+    if psi0 is not None and spins is not None:
+        raise ValueError("pass at most one of psi0 and spins")
+    if psi0 is None and spins is None:
+        psi0 = initial_state_rare(params)
+    n_sites = params.n_sea + 1
+    amps = spin_amplitudes(spins, n_sites) if spins is not None else None
+    prob = build_problem(params, order="engine", reduce=False)
+    psi_eng = reference_to_engine_state(psi0, prob.site_of_bit) if psi0 is not None else None
+    if isinstance(refs, str):
+        if refs != "initial":
+            raise ValueError('refs must be an array of kets or the string "initial"')
+        refs_eng = refs
+    else:
+        r = np.asarray(refs, dtype=np.complex128)
+        if r.ndim != 2 or r.shape[0] < 1 or r.shape[1] != 1 << n_sites:
+            raise ValueError(f"refs must have shape (K, {1 << n_sites}) with K >= 1")
+        refs_eng = np.stack([reference_to_engine_state(v, prob.site_of_bit) for v in r])
+    eng = _engine(_default_device() if device is None else device)
+    t, obs, _, _, ovl = _evolve_from(eng, params, psi_eng, amps, refs_eng)
+    return t, obs, ovl
 
 
 def simulate_rare_sequence(segments, psi0=None, spins=None, device: int | None = None):

@@ -32,13 +32,15 @@ def device_memory(device: int) -> Tuple[float, float]:
     return float(out[0]), float(out[1])
 
 
-def problem_bytes(prob: Problem, stored_initial_state: bool = False) -> float:
+def problem_bytes(prob: Problem, stored_initial_state: bool = False, overlap_refs: int = 0) -> float:
     """Upper estimate of one problem's device footprint in a context: 3 state buffers, one
     intermediate output of a two-output launch, the Walsh-Hadamard engine's 2 extra vectors or the
     2-tile hand-off ring (the larger: 2 vectors), plus tables and coefficients.
     ``stored_initial_state``: the problem will carry a stored initial state (Engine.set_initial_state
-    or continue_from_final): one more state-sized buffer (a product state costs none)."""
-    return 16.0 * (3 + 1 + 2 + (1 if stored_initial_state else 0)) * (1 << prob.n_qubits) + (4 << 20)
+    or continue_from_final): one more state-sized buffer (a product state costs none).
+    ``overlap_refs``: the reference states it will carry (Engine.set_overlap_refs): one state-sized
+    buffer each."""
+    return 16.0 * (3 + 1 + 2 + (1 if stored_initial_state else 0) + int(overlap_refs)) * (1 << prob.n_qubits) + (4 << 20)
 
 
 # A libdse evolve runs its persistent interval kernel only when every register that is not on the
@@ -292,6 +294,53 @@ class Engine:
     def pair_obs_problems(self) -> int:
         """Registers whose pair sums the last successful evolve produced."""
         return int(self._L.dse_pair_obs_problems(self._h))
+
+    # -- overlaps with stored reference states (include/dse.h, feature "overlap_obs") --
+    def set_overlap_refs(self, pid: int, refs) -> None:
+        """Register ``pid`` carries the reference states ``refs`` ((K, 2^n) complex, K <=
+        DSE_MAX_OVERLAP_REFS, used as given; a loopback partitioned register: shard 0's id and whole
+        states): every later evolve keeps <refs[k]|psi(t_j)> / ||psi(t_j)|| of every output.  The set
+        replaces the previous one; ``None`` or an empty array clears it."""
+        pid = self._pid(pid)
+        if refs is None or len(refs) == 0:
+            self._check(self._L.dse_set_overlap_refs(self._h, pid, 0, None))
+            return
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(refs, dtype=np.complex128)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[1] != dim:
+            raise ValueError(f"references must have shape (K, {dim})")
+        self._check(self._L.dse_set_overlap_refs(self._h, pid, x.shape[0], _lib.ptr(x)))
+
+    def overlap_refs(self, pid: int) -> int:
+        """K of register ``pid`` (0: none)."""
+        return self._check(self._L.dse_overlap_refs(self._h, self._pid(pid)))
+
+    def overlaps(self, pid: int, psi: np.ndarray) -> np.ndarray:
+        """(K,) complex: <refs[k]|psi> / ||psi|| of the given state (dse_overlaps: the tile kernel of
+        the evolve).  RuntimeError for a register without references."""
+        pid = self._pid(pid)
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        out = np.empty((2, max(self.overlap_refs(pid), 1)))
+        self._check(self._L.dse_overlaps(self._h, pid, _lib.ptr(x), _lib.ptr(out)))
+        return out[0] + 1j * out[1]
+
+    def overlap_traces(self, pid: int) -> np.ndarray:
+        """(K, n_t) complex128: <refs[k]|psi(t_j)> / ||psi(t_j)|| of register ``pid`` from the last
+        evolve (RuntimeError before one, after a failed one and for a register without references)."""
+        pid = self._pid(pid)
+        n_t = max(int(self._L.dse_overlap_outputs(self._h)), 0)
+        out = np.empty((2, max(self.overlap_refs(pid), 1), max(n_t, 1)))
+        self._check(self._L.dse_get_overlaps(self._h, pid, _lib.ptr(out)))
+        return out[0] + 1j * out[1]
+
+    def overlap_problems(self) -> int:
+        """Registers whose overlaps the last successful evolve produced."""
+        return int(self._L.dse_overlap_problems(self._h))
 
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
