@@ -92,46 +92,62 @@ def test_production_interval_kernel_matches_reference_n14(engine, golden, m, rea
     print(f"N=14 production path (M={m}): max |GPU - reference-H oracle| = {worst:.2e}")
 
 
+@pytest.mark.parametrize("span_tile", [0, -1])
 @pytest.mark.parametrize("m", [2, 1])
-def test_production_path_is_repeatable_in_one_context(engine, m):
+def test_production_path_is_repeatable_in_one_context(engine, m, span_tile):
     """The same evolve of the config-3 points, three times in one context (same allocations, same
     hand-off slots and flags): bitwise identical.  A build whose interval kernel read its
-    coefficient rows through scalar loads varied here at the 1e-10 level (tools/diag_repeat.py)."""
+    coefficient rows through scalar loads varied here at the 1e-10 level (tools/diag_repeat.py).
+    span_tile = 0: k_interval (whole registers); -1 (the default): the automatic span policy's
+    choice for nine registers."""
     t = np.linspace(0.0, 2e-4, 21)
     engine.clear()
     engine.set_option("outputs_per_launch", m)
+    engine.set_option("span_tile", span_tile)
     try:
         for variant in VARIANTS:
             for delta in DELTAS:
                 engine.add(pb.build_problem(_params(variant, delta, t)))
-        runs = [engine.evolve(t)[0] for _ in range(3)]
+        runs, stats = zip(*[engine.evolve(t) for _ in range(3)])
     finally:
         engine.set_option("outputs_per_launch", 2)
+        engine.set_option("span_tile", -1)
         engine.clear()
+    print(f"span_tile {span_tile}: span_problems = {[st['span_problems'] for st in stats]}")
+    if span_tile == 0:
+        assert all(st["mode"] == 1 and st["span_problems"] == 0 for st in stats)
     for r in runs[1:]:
         assert np.array_equal(r, runs[0])
 
 
-def test_reference_grid_intervals_match_fine_stepping_n14(engine):
+@pytest.mark.parametrize("span_tile", [0, -1])
+def test_reference_grid_intervals_match_fine_stepping_n14(engine, span_tile):
     """The full-sweep regime of config 3: the reference's own grid (t_final 30 s, 20000 outputs,
     sweep_sea_detuning.py:1223-1224) puts ~1e4 Chebyshev terms into one interval (alpha dt ~ 1e4,
     one output per launch).  Its first two intervals, on the production interval kernel for all
     three variants at delta 0 and 150 kHz, against the same evolutions stepped through 150
     sub-intervals each (10 us, two outputs per launch, ~100 terms per launch): the propagator is
-    exact at both degrees, so the observables agree to 1e-10 and the norm stays 1 to 1e-12."""
+    exact at both degrees, so the observables agree to 1e-10 and the norm stays 1 to 1e-12.
+    span_tile = 0: k_interval (whole registers); -1 (the default): the automatic span policy's choice
+    for six registers."""
     t_ref = np.linspace(0.0, 30.0, 20000)[:3]
     t_fine = np.concatenate([np.linspace(t_ref[0], t_ref[1], 151), np.linspace(t_ref[1], t_ref[2], 151)[1:]])
     assert t_fine[150] == t_ref[1] and t_fine[300] == t_ref[2]
     probs = [pb.build_problem(sweep_point_params(13, float(d), v, 30.0, 20000))
              for v in VARIANTS for d in (0.0, 150e3)]
     engine.clear()
+    engine.set_option("span_tile", span_tile)
     try:
         for p in probs:
             engine.add(p)
         coarse, st_c = engine.evolve(t_ref)
         fine, st_f = engine.evolve(t_fine)
     finally:
+        engine.set_option("span_tile", -1)
         engine.clear()
+    print(f"span_tile {span_tile}: span_problems = {st_c['span_problems']} (coarse), {st_f['span_problems']} (fine)")
+    if span_tile == 0:
+        assert st_c["span_problems"] == 0 and st_f["span_problems"] == 0
     assert st_c["mode"] == 1 and st_c["outputs_per_launch"] == 1 and st_c["max_degree"] > 5000
     assert st_f["mode"] == 1 and st_f["max_degree"] < 1000
     worst = float(np.max(np.abs(coarse[:, :6, :] - fine[:, :6, ::150])))

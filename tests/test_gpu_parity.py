@@ -158,8 +158,20 @@ def test_evolve_matches_exact_n12_center_on(engine, golden):
     assert 1e-7 < d_ref < 1e-3
 
 
-def test_evolve_tile_size_and_batch_invariance(engine):
-    """N = 14 sweep points: tile 12 vs 13 and batched vs single agree to rounding."""
+@pytest.mark.parametrize("span_tile", [0, -1])
+def test_evolve_tile_size_and_batch_invariance(engine, span_tile):
+    """N = 14 sweep points: tile 12 vs 13 and batched vs single agree to rounding.  span_tile = 0:
+    whole registers (tile 13 on k_interval); -1 (the default): the automatic span policy's choice."""
+    engine.set_option("span_tile", span_tile)
+    try:
+        _tile_size_and_batch_invariance(engine, span_tile)
+    finally:
+        engine.set_option("span_tile", -1)
+        engine.set_option("tile_bits", 13)
+        engine.set_option("streams", 4)
+
+
+def _tile_size_and_batch_invariance(engine, span_tile):
     t = np.linspace(0.0, 2e-5, 5)
     params = [sweep_point_params(13, d, v, 2e-5, 5) for d in (0.0, 150000.0) for v in VARIANTS]
     res = {}
@@ -168,7 +180,10 @@ def test_evolve_tile_size_and_batch_invariance(engine):
         engine.set_option("tile_bits", tb)
         for p in params:
             engine.add(pb.build_problem(p))
-        res[tb], _ = engine.evolve(t)
+        res[tb], st = engine.evolve(t)
+        print(f"tile_bits {tb} span_tile {span_tile}: mode {st['mode']}, span_problems = {st['span_problems']}")
+        if span_tile == 0:
+            assert st["span_problems"] == 0
     engine.set_option("tile_bits", 13)
     np.testing.assert_allclose(res[12], res[13], rtol=0, atol=1e-11)
     engine.clear()
@@ -234,10 +249,12 @@ def test_simulate_rare_drop_in_contract():
         simulate_rare(dataclasses.replace(p, steps=1))
 
 
+@pytest.mark.parametrize("span_tile", [0, -1])
 @pytest.mark.parametrize("n,tile_bits", [(11, 10), (12, 12), (13, 12), (14, 13)])
-def test_persistent_matches_streaming_and_expm(engine, n, tile_bits):
+def test_persistent_matches_streaming_and_expm(engine, n, tile_bits, span_tile):
     """The persistent interval kernel (1- and 2-tile registers, cross-tile hand-off) reproduces
-    the per-term streaming kernels and scipy's expm_multiply."""
+    the per-term streaming kernels and scipy's expm_multiply.  span_tile = 0: k_interval (whole
+    registers); -1 (the default): what the automatic span policy picks for three registers, k_span."""
     import scipy.sparse as sp
     from scipy.sparse.linalg import expm_multiply
     from quantumsimulations_amd.dipolar_ensemble_with_rare import problem_to_csr
@@ -245,6 +262,7 @@ def test_persistent_matches_streaming_and_expm(engine, n, tile_bits):
     t = np.linspace(0.0, 5e-4, 4)
     res, states = {}, {}
     engine.set_option("tile_bits", tile_bits)
+    engine.set_option("span_tile", span_tile)
     try:
         for pers in (0, 1):
             engine.clear()
@@ -253,10 +271,14 @@ def test_persistent_matches_streaming_and_expm(engine, n, tile_bits):
                 engine.add(p)
             res[pers], st = engine.evolve(t)
             assert st["mode"] == (1 if pers else (2 if tile_bits >= 12 and n > tile_bits else 0))
+            print(f"persistent {pers} span_tile {span_tile}: span_problems = {st['span_problems']}")
+            if span_tile == 0:
+                assert st["span_problems"] == 0
             states[pers] = [engine.state(i) for i in range(len(probs))]
     finally:
         engine.set_option("persistent", 1)
         engine.set_option("tile_bits", 13)
+        engine.set_option("span_tile", -1)
     np.testing.assert_allclose(res[1], res[0], rtol=0, atol=1e-11)
     psi0 = np.zeros(1 << n, dtype=complex)
     psi0[probs[1].psi0_index] = 1.0
@@ -264,22 +286,31 @@ def test_persistent_matches_streaming_and_expm(engine, n, tile_bits):
     assert np.max(np.abs(states[1][1] - ref)) < 1e-10
 
 
-def test_persistent_path_is_bitwise_deterministic(engine):
+@pytest.mark.parametrize("span_tile", [0, -1])
+def test_persistent_path_is_bitwise_deterministic(engine, span_tile):
     """Repeated evolves of 2-tile problems (cross-workgroup hand-off every term) give identical
     bits, and agree with the per-term streaming kernels to rounding.  Guards the interval
-    kernel's hand-off protocol and its register budget (a spilling build drifted by ~1e-9)."""
+    kernel's hand-off protocol and its register budget (a spilling build drifted by ~1e-9) at
+    span_tile = 0; at -1 (the default) the automatic span policy's choice for eight registers."""
     t = np.linspace(0.0, 2e-5, 5)
     params = [sweep_point_params(13, d, v, 2e-5, 5)
               for d in (0.0, 50e3, 100e3, 150e3) for v in ("center_on", "shell_off")]
     engine.clear()
     engine.set_option("tile_bits", 13)
-    for p in params:
-        engine.add(pb.build_problem(p))
-    runs = []
-    for _ in range(3):
-        obs, st = engine.evolve(t)
-        assert st["mode"] == 1
-        runs.append(obs)
+    engine.set_option("span_tile", span_tile)
+    try:
+        for p in params:
+            engine.add(pb.build_problem(p))
+        runs = []
+        for _ in range(3):
+            obs, st = engine.evolve(t)
+            assert st["mode"] == 1
+            print(f"span_tile {span_tile}: span_problems = {st['span_problems']}")
+            if span_tile == 0:
+                assert st["span_problems"] == 0
+            runs.append(obs)
+    finally:
+        engine.set_option("span_tile", -1)
     for o in runs[1:]:
         assert np.array_equal(o, runs[0])
     engine.set_option("persistent", 0)
