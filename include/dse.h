@@ -456,7 +456,7 @@ int dse_overlap_outputs(const dse_ctx* ctx);
  * counts once), 0 when there are none. */
 int dse_overlap_problems(const dse_ctx* ctx);
 /* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
- * "pair_obs", "overlap_obs". */
+ * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian". */
 int dse_has_feature(const char* name);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);
@@ -498,6 +498,56 @@ int dse_continue_from_final(dse_ctx* ctx, int problem);
 /* The state the next dse_evolve would start from (the basis state, the stored state, or the
  * product state materialised by its kernel): test and diagnostic hook. */
 int dse_get_initial_state(dse_ctx* ctx, int problem, double* psi_out);
+
+/* ---- hard pulses and piecewise-constant H (features "pulse", "set_hamiltonian") -----------------
+ * An instantaneous rotation of chosen spins between two periods of evolution (Hahn echo, CPMG, a
+ * z-phase increment, a read-out pulse), and a new H for a problem that keeps its state: together a
+ * pulse sequence whose state never leaves the device.  No reference counterpart (the reference has
+ * one time-independent H per call).
+ *
+ * dse_apply_pulse transforms the state the next dse_evolve starts from by U = (x)_b U_b:
+ *   u[8 b + ...] = (re u00, im u00, re u01, im u01, re u10, im u10, re u11, im u11) of register bit b,
+ *   row / column index = bit value (0 = spin up): psi'(.., v, ..) = sum_w u_vw psi(.., w, ..).
+ *   - A stored state (dse_set_initial_state, dse_continue_from_final): k_pulse (dse_pulse.hip) runs in
+ *     place on it, one launch per pass of dse_pulse_plan; nothing state-sized is allocated or crosses
+ *     the host.  A loopback partitioned register: shard 0's id, all shards transformed.
+ *   - A product state stays one: a_b <- U_b a_b on the host, the 4 n doubles uploaded again.
+ *   - The basis state psi0_index becomes the product state whose pair for bit b is column
+ *     bit_b(psi0_index) of U_b.  The identity (every U_b exactly 1) changes nothing, whatever the start.
+ *   - The matrices are used as given: unitarity is not checked (2 Ix_b is a legal factor).
+ *   - DSE_ERR_ARG, the state left as it was: a non-finite entry, a matrix that is all zero, on the two
+ *     host paths a resulting zero or non-finite amplitude pair, a bad id, a non-zero shard id of a
+ *     loopback register, a register partitioned over processes.  A stored state that a singular pulse
+ *     maps to zero is NOT detected: the next dse_evolve then reports state_norm 0 and undefined
+ *     expectations.
+ *   - A pulse before any dse_evolve and on a problem without a custom state is accepted.  The final
+ *     state of the last evolve (dse_get_state) is not touched. */
+int dse_apply_pulse(dse_ctx* ctx, int problem, const double* u /* [8 n] */);
+/* out[0] = passes (kernel launches), out[1] = their HIP-event time in ms, out[2] = the bytes they
+ * moved (32 per amplitude and pass) of the last dse_apply_pulse of the context; zeros for the host
+ * paths, the identity and a refused call. */
+int dse_pulse_stats(const dse_ctx* ctx, double* out /* [3] */);
+/* Host only, like dse_wht_plan: the passes of a pulse on a register of n_local local and shard_bits
+ * (0..3) shard bits (register bit n_local + s = shard bit s).  active_mask: the bits whose matrix is not
+ * the identity; diag_mask: those of them whose matrix is diagonal (a subset, DSE_ERR_ARG otherwise).
+ * Returns the number of passes G (0: the identity) and writes, for g < G,
+ *   groups_out[g][0]      the carried low bits c (0: group 0, the low 12 bits)
+ *   groups_out[g][1 + q]  the register bit of tile bit q < 12 (-1: none, registers below 12 bits)
+ *   groups_out[g][13]     the mask of tile bits q the pass transforms (0: a pass for diagonal
+ *                         matrices only).
+ * The first pass also applies every diagonal matrix's phase. */
+int dse_pulse_plan(int n_local, int shard_bits, uint64_t active_mask, uint64_t diag_mask,
+                   int32_t* groups_out /* [4][14] */);
+/* Replaces the tables of a problem (arrays as in dse_add_problem, validated the same way; on failure
+ * the old H stays): the spectral bounds and the flop count follow, on every shard of a loopback
+ * register (shard 0's id).  Kept: n, psi0_index, the masks, the shard layout, the initial state, the
+ * overlap references, the options.  The device layout is dropped and rebuilt by the next dse_evolve,
+ * which is bitwise what a fresh context with the new tables and the same initial state gives; the
+ * previous final state goes with it (dse_get_state and dse_continue_from_final return DSE_ERR_STATE
+ * until the next evolve: continue first, then change H).  Not available for a register partitioned
+ * over processes (DSE_ERR_ARG). */
+int dse_set_hamiltonian(dse_ctx* ctx, int problem, const double* field, const double* zz,
+                        const double* pair, const double* flip, double shift);
 
 /* Energy of the final state after dse_evolve, on the device: e_out[0] = <psi|H|psi> / <psi|psi>,
  * e_out[1] = <psi|psi> (a partitioned loopback register: shard 0's id, whole register).  Unitary

@@ -36,6 +36,7 @@ EXPORTED = (
     "dse_has_feature",
     "dse_set_overlap_refs", "dse_overlap_refs", "dse_overlaps", "dse_get_overlaps",
     "dse_overlap_outputs", "dse_overlap_problems",
+    "dse_apply_pulse", "dse_pulse_stats", "dse_pulse_plan", "dse_set_hamiltonian",
 )
 DSE_MAX_OVERLAP_REFS = 16
 DSE_DIST_ID_BYTES = 128
@@ -145,6 +146,10 @@ def _declare(lib):
         "dse_dist_init": (C.c_int, [_vp, C.c_int, C.c_int, C.c_char_p]),
         "dse_problem_dim": (C.c_int64, [_vp, C.c_int]),
         "dse_wht_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+        "dse_apply_pulse": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_pulse_stats": (C.c_int, [_vp, _dp]),
+        "dse_pulse_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
+        "dse_set_hamiltonian": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -172,6 +177,8 @@ def lib():
                 raise ImportError("libdse.so predates dse_has_feature (two-spin correlators); rebuild it")
             if not hasattr(handle, "dse_set_overlap_refs"):
                 raise ImportError("libdse.so predates the overlaps with reference states; rebuild it")
+            if not hasattr(handle, "dse_apply_pulse"):
+                raise ImportError("libdse.so predates the hard pulses (dse_apply_pulse); rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
@@ -181,7 +188,7 @@ def lib():
 
 def has_feature(name: str) -> bool:
     """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs",
-    "overlap_obs")."""
+    "overlap_obs", "pulse", "set_hamiltonian")."""
     return bool(lib().dse_has_feature(name.encode()))
 
 

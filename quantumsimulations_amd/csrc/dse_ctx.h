@@ -358,6 +358,11 @@ struct dse_ctx {
   double dense_out_ms = 0.0;  // last evolve: host wall time of the dense engine's output stage
   std::vector<hipStream_t> eig_st;
   std::vector<rocblas_handle> eig_h;
+  // hard pulses (dse_pulse.hip): the table a call's passes read, the events around them, and the last
+  // call's passes, HIP-event ms and bytes (dse_pulse_stats); released by dse_destroy
+  dse::rt::DevBuf<dse::PulseTab> d_pulse_tab;
+  hipEvent_t pulse_ev[2] = {nullptr, nullptr};
+  double pulse_stats[3] = {0.0, 0.0, 0.0};
 };
 
 #pragma GCC visibility push(hidden)

@@ -335,4 +335,40 @@ hipError_t launch_obs_overlap(int L, const DevProb* probs, const int2* items, in
 hipError_t launch_dot(const double2* a, const double2* b, size_t n, double* partial, int blocks,
                       hipStream_t st);
 
+// ---- hard pulses (dse_pulse.hip): U = (x)_b U_b in place on a state ------------------------------
+constexpr int kPulseTB = 12;          // tile bits of a pass: 2^12 amplitudes, 64 KiB of LDS per workgroup
+constexpr int kPulseTile = 1 << kPulseTB;
+constexpr int kPulseMinCarry = 2;     // a group of high bits carries at least this many low bits (64-B runs)
+constexpr int kPulseMaxGroups = 4;    // group 0 and ceil((34 - 12) / 10) groups of high bits
+// what every pass of one call reads from device memory (the parts indexed at run time)
+struct PulseTab {
+  double2* base[kMaxShards];  // the shards' buffers
+  double d[kMaxQubits][4];    // (re u00, im u00, re u11, im u11) of every bit: the diagonal matrices' phase
+  double u[kMaxQubits][8];    // every bit's matrix (k_pulse_small)
+};
+// one pass: the kernel's argument
+struct PulsePass {
+  int pos[kPulseTB];          // register bit of tile bit q
+  double u[kPulseTB][8];      // its matrix
+  double2* base0;             // the buffer of an unpartitioned register
+  uint64_t outer;             // the register bits outside the tile (the workgroup index is spread over them)
+  uint64_t diag;              // the bits whose diagonal matrix this pass applies (0: another pass does)
+  uint32_t bfly;              // the tile bits this pass transforms
+  int n_local, shard_bits;
+};
+struct PulseGroup {
+  int c;                      // carried low bits (0: group 0 and the small path)
+  int pos[kPulseTB];          // register bit of tile bit q (-1: none, registers of fewer than 12 bits)
+  uint32_t bfly;              // the tile bits the pass transforms
+  uint64_t active;            // the register bits it is launched for
+};
+struct PulsePlan {
+  int passes;
+  bool small;                 // the whole register in one workgroup (k_pulse_small)
+  PulseGroup grp[kPulseMaxGroups];
+};
+int pulse_plan(int n_local, int shard_bits, uint64_t active, uint64_t diag, PulsePlan& plan);
+hipError_t launch_pulse(double2* const* base, int n_local, int shard_bits, const double* u, uint64_t active,
+                        uint64_t diag, PulseTab* tab, hipStream_t st, int* passes);
+
 }  // namespace dse

@@ -1282,6 +1282,9 @@ void dse_destroy(dse_ctx* ctx) {
   free_device(ctx);
   for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p);
   ctx->d_mx.release();
+  ctx->d_pulse_tab.release();
+  for (auto& e : ctx->pulse_ev)
+    if (e) (void)hipEventDestroy(e), e = nullptr;
   destroy_lanes(ctx);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
   delete ctx;
@@ -2583,7 +2586,8 @@ int dse_get_overlaps(dse_ctx* ctx, int problem, double* out) { return obs_family
 int dse_has_feature(const char* name) {
   if (!name) return 0;
   const std::string k(name);
-  return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs";
+  return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs" || k == "pulse" ||
+         k == "set_hamiltonian";
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -4220,6 +4224,108 @@ int dse_get_initial_state(dse_ctx* ctx, int problem, double* psi_out) {
       if ((P.psi0 >> P.n_local) == (uint64_t)P.shard_rank)
         dst[P.psi0 & ((uint64_t(1) << P.n_local) - 1)] = make_double2(1.0, 0.0);
     }
+  }
+  return DSE_OK;
+}
+
+// ---- hard pulses and a new H for a problem (features "pulse", "set_hamiltonian") ------------------
+
+int dse_apply_pulse(dse_ctx* ctx, int problem, const double* u) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_apply_pulse");
+  if (rc) return rc;
+  if (!u) return fail(ctx, DSE_ERR_ARG, "dse_apply_pulse: null matrices");
+  const HostProblem& P0 = ctx->probs[first];
+  const int n = P0.n;
+  uint64_t active = 0, diag = 0;
+  for (int b = 0; b < n; ++b) {
+    const double* m = u + 8 * b;
+    bool zero = true;
+    for (int i = 0; i < 8; ++i) {
+      if (!std::isfinite(m[i])) return fail(ctx, DSE_ERR_ARG, "dse_apply_pulse: non-finite matrix entry");
+      zero = zero && m[i] == 0.0;
+    }
+    if (zero) return fail(ctx, DSE_ERR_ARG, "dse_apply_pulse: the matrix of bit " + std::to_string(b) + " is zero");
+    const bool dg = m[2] == 0.0 && m[3] == 0.0 && m[4] == 0.0 && m[5] == 0.0;
+    const bool id = dg && m[0] == 1.0 && m[1] == 0.0 && m[6] == 1.0 && m[7] == 0.0;
+    if (!id) active |= uint64_t(1) << b;
+    if (dg && !id) diag |= uint64_t(1) << b;
+  }
+  ctx->pulse_stats[0] = ctx->pulse_stats[1] = ctx->pulse_stats[2] = 0.0;
+  if (!active) return DSE_OK;  // the identity: nothing changes, whatever the kind of start
+  if (P0.init_kind != 1) {
+    // a product state stays one: a_b <- U_b a_b; the basis state becomes the product of the columns
+    // bit_b(psi0) of the U_b
+    std::vector<double> amp(4 * (size_t)n);
+    for (int b = 0; b < n; ++b) {
+      const double* m = u + 8 * b;
+      double a[4] = {1.0, 0.0, 0.0, 0.0};
+      if (P0.init_kind == 2) std::copy(P0.init_amp.begin() + 4 * b, P0.init_amp.begin() + 4 * b + 4, a);
+      else if ((P0.psi0 >> b) & 1) a[0] = 0.0, a[2] = 1.0;
+      double* o = &amp[4 * (size_t)b];
+      for (int v = 0; v < 2; ++v) {
+        const double* r = m + 4 * v;  // row v: (re u_v0, im u_v0, re u_v1, im u_v1)
+        o[2 * v] = (r[0] * a[0] - r[1] * a[1]) + (r[2] * a[2] - r[3] * a[3]);
+        o[2 * v + 1] = (r[0] * a[1] + r[1] * a[0]) + (r[2] * a[3] + r[3] * a[2]);
+      }
+      if (!(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]) && std::isfinite(o[3])))
+        return fail(ctx, DSE_ERR_ARG, "dse_apply_pulse: non-finite amplitude of bit " + std::to_string(b));
+      if (o[0] == 0.0 && o[1] == 0.0 && o[2] == 0.0 && o[3] == 0.0)
+        return fail(ctx, DSE_ERR_ARG, "dse_apply_pulse: the pulse maps the amplitude pair of bit " + std::to_string(b) + " to zero");
+    }
+    return dse_set_initial_product(ctx, problem, amp.data());
+  }
+  HIPC(hipSetDevice(ctx->device));
+  if ((rc = ctx->d_pulse_tab.reserve(ctx, 1, "pulse table allocation failed"))) return rc;
+  for (auto& e : ctx->pulse_ev)
+    if (!e) HIPC(hipEventCreate(&e));
+  double2* base[kMaxShards] = {};
+  for (int i = 0; i < count; ++i) base[i] = ctx->probs[first + i].init_state;
+  hipStream_t st = ctx->lanes[0].stream;
+  int passes = 0;
+  HIPC(hipEventRecord(ctx->pulse_ev[0], st));
+  HIPC(launch_pulse(base, P0.n_local, count > 1 ? P0.shard_bits : 0, u, active, diag, ctx->d_pulse_tab.p, st, &passes));
+  HIPC(hipEventRecord(ctx->pulse_ev[1], st));
+  HIPC(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIPC(hipEventElapsedTime(&ms, ctx->pulse_ev[0], ctx->pulse_ev[1]));
+  ctx->pulse_stats[0] = passes;
+  ctx->pulse_stats[1] = ms;
+  ctx->pulse_stats[2] = 32.0 * (double)passes * std::ldexp(1.0, n);
+  return DSE_OK;
+}
+
+int dse_pulse_stats(const dse_ctx* ctx, double* out) {
+  if (!ctx || !out) return DSE_ERR_ARG;
+  std::copy(ctx->pulse_stats, ctx->pulse_stats + 3, out);
+  return DSE_OK;
+}
+
+int dse_set_hamiltonian(dse_ctx* ctx, int problem, const double* field, const double* zz, const double* pair,
+                        const double* flip, double shift) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_hamiltonian");
+  if (rc) return rc;
+  const HostProblem& P0 = ctx->probs[first];
+  HostProblem q;  // validated as dse_add_problem validates; the old H stays on failure
+  if ((rc = make_problem(ctx, q, P0.n, field, zz, pair, flip, shift, P0.psi0, P0.sea_mask, P0.rare_bit, P0.rare_z)))
+    return rc;
+  (void)hipSetDevice(ctx->device);
+  (void)sync_all(ctx);
+  free_device(ctx);  // the device layout is rebuilt lazily; the previous final state goes with it
+  for (int i = 0; i < count; ++i) {
+    // a problem as dse_add_problem(_sharded) makes it (free_device left no device pointer behind) that
+    // takes over the shard layout and what belongs to the problem beyond its tables
+    HostProblem& P = ctx->probs[first + i];
+    HostProblem f = q;
+    f.shard_bits = P.shard_bits, f.shard_rank = P.shard_rank, f.n_local = P.n_local;
+    f.group_first = P.group_first, f.dist = P.dist;
+    f.init_kind = P.init_kind, f.init_state = P.init_state, f.d_init_amp = P.d_init_amp;
+    f.init_amp = std::move(P.init_amp);
+    f.ovl_refs = std::move(P.ovl_refs), f.d_ovl_tab = P.d_ovl_tab;
+    P = std::move(f);
   }
   return DSE_OK;
 }

@@ -40,7 +40,7 @@ __all__ = [
     "dipolar_couplings_from_positions", "simulate_rare", "simulate_rare_batch", "simulate_rare_sites",
     "simulate_rare_pairs",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
-    "simulate_rare_from", "simulate_rare_sequence", "simulate_rare_overlaps",
+    "simulate_rare_from", "simulate_rare_sequence", "simulate_rare_overlaps", "rotation_matrices",
 ]
 
 _ENGINES: Dict[int, object] = {}
@@ -409,28 +409,108 @@ def simulate_rare_overlaps(params: DipolarRareParams, refs, psi0=None, spins=Non
     return t, obs, ovl
 
 
-def simulate_rare_sequence(segments, psi0=None, spins=None, device: int | None = None):
+def rotation_matrices(vecs) -> np.ndarray:
+    """(n_sites, 2, 2) matrices exp(-i theta n.sigma / 2) of the rotation vectors ``vecs``
+    (n_sites, 3), row s = theta n of site s (the rotation of a hard pulse of flip angle theta about
+    the axis n); a zero row is the identity.  Row / column 0 = spin up.  A rotation about z comes
+    out exactly diagonal."""
+    v = np.asarray(vecs)
+    if v.ndim != 2 or v.shape[1] != 3 or np.iscomplexobj(v):
+        raise ValueError("rotation vectors must be a real array of shape (n_sites, 3)")
+    v = np.array(v, dtype=np.float64)
+    if not np.all(np.isfinite(v)):
+        raise ValueError("rotation vectors must be finite")
+    theta = np.linalg.norm(v, axis=1)
+    c = np.cos(0.5 * theta)
+    # sin(theta / 2) n = (sin(theta / 2) / theta) v, 1/2 v at theta = 0
+    s = v * np.where(theta > 0.0, np.sin(0.5 * theta) / np.where(theta > 0.0, theta, 1.0), 0.5)[:, None]
+    u = np.empty((v.shape[0], 2, 2), dtype=np.complex128)
+    u[:, 0, 0] = c - 1j * s[:, 2]
+    u[:, 0, 1] = -s[:, 1] - 1j * s[:, 0]
+    u[:, 1, 0] = s[:, 1] - 1j * s[:, 0]
+    u[:, 1, 1] = c + 1j * s[:, 2]
+    return u
+
+
+def pulse_matrices_by_bit(mats_by_site: np.ndarray, site_of_bit: np.ndarray) -> np.ndarray:
+    """Per-site pulse matrices (n_sites, 2, 2), sites in the reference's order, as the (n, 2, 2) array
+    Engine.apply_pulse takes: row b = the matrix of the site register bit b holds."""
+    sob = np.asarray(site_of_bit, dtype=np.int64)
+    m = np.asarray(mats_by_site, dtype=np.complex128)
+    if m.ndim != 3 or m.shape[1:] != (2, 2) or sorted(sob.tolist()) != list(range(m.shape[0])):
+        raise ValueError("matrices must have shape (n_sites, 2, 2) and site_of_bit be a permutation of the sites")
+    return np.ascontiguousarray(m[sob])
+
+
+def _check_pulses(pulses, n_segments: int, n_sites: int) -> list:
+    """One entry per segment: None or the (n_sites, 2, 2) matrices of the pulse before it."""
+    if pulses is None:
+        return [None] * n_segments
+    entries = list(pulses)
+    if len(entries) != n_segments:
+        raise ValueError(f"pulses must have one entry per segment ({n_segments}), got {len(entries)}")
+    out = []
+    for k, e in enumerate(entries):
+        if e is None:
+            out.append(None)
+            continue
+        a = np.asarray(e)
+        if a.shape == (n_sites, 3):
+            out.append(rotation_matrices(a))
+        elif a.shape == (n_sites, 2, 2):
+            m = np.array(a, dtype=np.complex128)
+            if not np.all(np.isfinite(m)):
+                raise ValueError(f"pulse {k}: non-finite matrix entry")
+            out.append(m)
+        else:
+            raise ValueError(f"pulse {k} must be None, rotation vectors ({n_sites}, 3) or matrices ({n_sites}, 2, 2)")
+    return out
+
+
+def simulate_rare_sequence(segments, psi0=None, spins=None, device: int | None = None, pulses=None):
     """A pulse sequence: piecewise-constant Hamiltonians, segment k starting from segment k - 1's
-    final state.
+    final state, with an optional hard pulse before each segment.
 
     ``segments``: DipolarRareParams of the same spins (n_sea, geometry flags, gyromagnetic ratios
     and couplings equal, ValueError otherwise) that differ in drives, phases, detunings and their
-    own (t_final, steps).  The start is ``psi0`` or ``spins`` as in simulate_rare_from.  Returns
+    own (t_final, steps).  The start is ``psi0`` or ``spins`` as in simulate_rare_from.
+    ``pulses``: None, or one entry per segment, applied to the state before that segment starts:
+    None, rotation vectors (n_sites, 3) (rotation_matrices: theta n per site, a zero row leaves the
+    spin alone) or matrices (n_sites, 2, 2) used as given; sites in the reference's order.  A wrong
+    length or shape is a ValueError before a device is touched.  Returns
     ``([(t_0, obs_0), (t_1, obs_1), ...], psi_final)``: the times of segment k are offset by the
     preceding segments' t_final (a junction time appears in both neighbours), psi_final is in the
-    reference's basis order.  The state is carried from one segment to the next through the host.
+    reference's basis order.  The state stays on the device: the register is added once, and per
+    segment its tables are replaced (Engine.set_hamiltonian), the pulse applied (Engine.apply_pulse),
+    the segment evolved and its final state made the next start (Engine.continue_from_final).
     Every segment is in its own rotating frame (its omega_rf); the caller keeps them consistent."""
     segs = _check_segments(segments)
     _check_start(psi0, spins)
     n_sites = segs[0].n_sea + 1
+    mats = _check_pulses(pulses, len(segs), n_sites)
     amps = spin_amplitudes(spins, n_sites) if spins is not None else None
-    prob0 = build_problem(segs[0], order="engine", reduce=False)
-    psi_eng = reference_to_engine_state(psi0, prob0.site_of_bit) if psi0 is not None else None
+    probs = [build_problem(p, order="engine", reduce=False) for p in segs]
+    psi_eng = reference_to_engine_state(psi0, probs[0].site_of_bit) if psi0 is not None else None
     eng = _engine(_default_device() if device is None else device)
     out, t_off = [], 0.0
-    for p in segs:
-        t, obs, psi_eng, prob = _evolve_from(eng, p, psi_eng, amps)
-        amps = None
-        out.append((t + t_off, obs))
-        t_off += float(p.t_final)
-    return out, engine_to_reference_state(psi_eng, prob.site_of_bit)
+    eng.clear()
+    try:
+        pid = eng.add(probs[0])
+        if psi_eng is not None:
+            eng.set_initial_state(pid, psi_eng)
+        else:
+            eng.set_initial_product(pid, amps[probs[0].site_of_bit])
+        for k, (p, prob) in enumerate(zip(segs, probs)):
+            if k:
+                eng.continue_from_final(pid)
+                eng.set_hamiltonian(pid, prob)
+            if mats[k] is not None:
+                eng.apply_pulse(pid, pulse_matrices_by_bit(mats[k], prob.site_of_bit))
+            t = time_grid(p)
+            obs, _ = eng.evolve(t, tol=_tol())
+            out.append((t + t_off, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}))
+            t_off += float(p.t_final)
+        final = eng.state(pid)
+    finally:
+        eng.clear()
+    return out, engine_to_reference_state(final, probs[-1].site_of_bit)

@@ -390,6 +390,41 @@ class Engine:
         self._check(self._L.dse_get_initial_state(self._h, pid, _lib.ptr(out)))
         return out
 
+    # -- hard pulses and a new H for a problem (include/dse.h, features "pulse", "set_hamiltonian") --
+    def apply_pulse(self, pid: int, mats) -> None:
+        """The state the next evolve of register ``pid`` starts from becomes U psi, U the tensor
+        product of ``mats[b]`` over the register bits b (``mats``: (n, 2, 2) complex, row / column
+        index = bit value, 0 = spin up; used as given, unitary or not).  A stored state is
+        transformed in place on the device, a product state stays one, the basis state becomes a
+        product state (dse_apply_pulse).  ``rotation_matrices`` makes ``mats`` from rotation vectors."""
+        pid = self._pid(pid)
+        n = self.problems[pid].n_qubits
+        u = np.ascontiguousarray(mats, dtype=np.complex128)
+        if u.shape != (n, 2, 2):
+            raise ValueError(f"matrices must have shape ({n}, 2, 2)")
+        self._check(self._L.dse_apply_pulse(self._h, pid, _lib.ptr(u)))
+
+    def pulse_stats(self) -> Dict[str, float]:
+        """Passes (kernel launches), their HIP-event time in ms and the bytes they moved, of the last
+        apply_pulse (zeros when it ran on the host: product and basis starts, the identity)."""
+        out = np.zeros(3)
+        self._check(self._L.dse_pulse_stats(self._h, _lib.ptr(out)))
+        return {"passes": int(out[0]), "ms": float(out[1]), "bytes": float(out[2])}
+
+    def set_hamiltonian(self, pid: int, prob: Problem) -> None:
+        """Register ``pid`` gets the tables of ``prob`` (the same number of qubits); it keeps its
+        initial state, overlap references, masks and shard layout.  The final state of the last evolve
+        is dropped: call continue_from_final first (dse_set_hamiltonian)."""
+        pid = self._pid(pid)
+        if prob.n_qubits != self.problems[pid].n_qubits:
+            raise ValueError("the new tables must describe a register of the same size")
+        tabs = self._tables(prob)
+        self._check(self._L.dse_set_hamiltonian(self._h, pid, *[_lib.ptr(a) for a in tabs], float(prob.shift)))
+        old, i = self.problems[pid], pid
+        while i < len(self.problems) and self.problems[i] is old:  # the shards of a loopback register follow
+            self.problems[i] = prob
+            i += 1
+
     def energy(self, pid: int) -> Tuple[float, float]:
         """(<psi|H|psi> / <psi|psi>, <psi|psi>) of the final state after evolve, on the device."""
         out = np.empty(2)
