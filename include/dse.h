@@ -46,11 +46,13 @@ extern "C" {
  * Later additions leave both numbers and dse_stats alone (custom_init_problems stays its last field):
  * a caller discovers them by name with dse_has_feature, and what would have been a stats counter is
  * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems; the overlaps with
- * reference states: feature "overlap_obs", dse_overlap_problems). */
+ * reference states: feature "overlap_obs", dse_overlap_problems; the operator strings: feature
+ * "op_strings", dse_op_string_problems). */
 #define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
 #define DSE_MAX_OVERLAP_REFS 16 /* reference states per problem (dse_set_overlap_refs) */
+#define DSE_MAX_OP_STRINGS 64   /* operator strings per problem (dse_set_op_strings) */
 
 enum dse_status {
   DSE_OK = 0,
@@ -455,8 +457,71 @@ int dse_overlap_outputs(const dse_ctx* ctx);
 /* Registers whose overlaps the last successful dse_evolve produced (a loopback partitioned register
  * counts once), 0 when there are none. */
 int dse_overlap_problems(const dse_ctx* ctx);
+/* ---- expectation values of operator strings (feature "op_strings") ---------------------------
+ * A string assigns to every register bit b one spin-1/2 operator O_b out of eight (bit value 0 = up,
+ * as everywhere in this header); its value on a state psi is the complex number
+ *     v = <psi| prod_b O_b |psi> / <psi|psi>.
+ * Multi-spin order <Iz Iz Iz ...>, multiple-quantum coherences (products of I+-), populations of a
+ * spin configuration on a subset (products of Ea / Eb), and through the 4^m - 1 strings over
+ * {Ix, Iy, Iz} on m spins their full reduced density matrix.  A one-factor string reproduces
+ * dse_site_observables, Iz Iz / I+ I- / I+ I+ reproduce dse_pair_observables.
+ * A problem may carry K <= DSE_MAX_OP_STRINGS strings; every dse_evolve then also keeps v_k(t_j) for
+ * every output time.
+ *   - The strings belong to the problem like the overlap references: kept over repeated evolves and
+ *     over dse_set_hamiltonian, replaced as a set, dropped by dse_clear.  Storage: one table of 48 K
+ *     bytes per register (per shard of a loopback register).
+ *   - With no strings in the context nothing is allocated and no kernel is added; with them the
+ *     aggregates, the "site_obs" / "pair_obs" / overlap traces and the final state are bitwise what
+ *     they are without, and no engine choice reads them.  Registers of one context may hold different
+ *     K, 0 included.
+ *   - Costs one more read of the state per output, one more per string that flips a bit above the
+ *     tile, and an arena of 2 K_max + 2 doubles per tile and output slot.
+ *   - dse_evolve returns DSE_ERR_ARG before any work for a context that holds both strings and a
+ *     register partitioned over processes (shard_rank >= 0).
+ *   - Sums of strings with coefficients are the caller's: add the values on the host. */
+enum dse_site_op {
+  DSE_OP_1 = 0,  /* identity                      */
+  DSE_OP_X = 1,  /* Ix = (I+ + I-) / 2            */
+  DSE_OP_Y = 2,  /* Iy = (I+ - I-) / 2i           */
+  DSE_OP_Z = 3,  /* Iz = (Ea - Eb) / 2            */
+  DSE_OP_P = 4,  /* I+ = |up><down|               */
+  DSE_OP_M = 5,  /* I- = |down><up|               */
+  DSE_OP_EA = 6, /* Ea = |up><up|                 */
+  DSE_OP_EB = 7  /* Eb = |down><down|             */
+};
+/* ops: [k][n], ops[s * n + b] the dse_site_op code of register bit b in string s; k = 0 or
+ * ops = NULL clears.  An all-identity string is legal (its value is 1).  DSE_ERR_ARG for a bad id, k
+ * above the cap, a code above 7, a non-zero shard id of a loopback register (shard 0's id, the codes
+ * of all n bits) and a register partitioned over processes; a failed allocation leaves the previous
+ * set in place. */
+int dse_set_op_strings(dse_ctx* ctx, int problem, int k, const uint8_t* ops);
+/* K of the problem (0: none), or DSE_ERR_ARG for a bad id. */
+int dse_op_strings(const dse_ctx* ctx, int problem);
+/* The values of the problem's strings on an arbitrary state psi (2^n interleaved complex): out[2][K],
+ * Re block then Im block (the hook beside dse_overlaps; runs the tile kernel of the evolve;
+ * DSE_ERR_STATE for a problem without strings). */
+int dse_op_string_values(dse_ctx* ctx, int problem, const double* psi, double* out);
+/* After dse_evolve: out[2][K][n_t], Re block then Im block of v_k(t_j) (a loopback partitioned
+ * register: shard 0's id).  The lifetime rules of dse_get_overlaps: DSE_ERR_STATE before an evolve,
+ * for a problem without strings, and after any dse_evolve that did not return DSE_OK.  After the
+ * re-run that follows a hand-off timeout the results are the re-run's (the dense engine's registers
+ * keep their first-pass results, like their aggregates). */
+int dse_get_op_strings(dse_ctx* ctx, int problem, double* out);
+/* n_t of the results dse_get_op_strings would return, 0 when there are none. */
+int dse_op_string_outputs(const dse_ctx* ctx);
+/* Registers whose string values the last successful dse_evolve produced (a loopback partitioned
+ * register counts once), 0 when there are none. */
+int dse_op_string_problems(const dse_ctx* ctx);
+/* Host only: the compiler of one string of n codes (ops[b]: register bit b) into the masks and the
+ * prefactor of
+ *     <psi| prod_b O_b |psi> = pre * sum_{x : (x & cm) == cv} (-1)^popcount(x & zm) conj(psi_x) psi_{x ^ xm}
+ * masks[4] = xm (bits of Ix, Iy, I+, I-: the flips), zm (Iz, Iy: the signs), cm (I+, I-, Ea, Eb: the
+ * selected bits), cv (I-, Eb: their required value in x); pre[2] = Re, Im of
+ * (1/2)^(#Ix + #Iy + #Iz) (-i)^#Iy.  DSE_ERR_ARG for n outside 1..DSE_MAX_QUBITS, a null pointer or a
+ * code above 7. */
+int dse_op_string_masks(int n, const uint8_t* ops, uint64_t* masks, double* pre);
 /* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
- * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian". */
+ * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian", "op_strings". */
 int dse_has_feature(const char* name);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);

@@ -37,8 +37,13 @@ EXPORTED = (
     "dse_set_overlap_refs", "dse_overlap_refs", "dse_overlaps", "dse_get_overlaps",
     "dse_overlap_outputs", "dse_overlap_problems",
     "dse_apply_pulse", "dse_pulse_stats", "dse_pulse_plan", "dse_set_hamiltonian",
+    "dse_set_op_strings", "dse_op_strings", "dse_op_string_values", "dse_get_op_strings",
+    "dse_op_string_outputs", "dse_op_string_problems", "dse_op_string_masks",
 )
 DSE_MAX_OVERLAP_REFS = 16
+DSE_MAX_OP_STRINGS = 64
+# enum dse_site_op: the code of a register bit in an operator string
+DSE_OP_1, DSE_OP_X, DSE_OP_Y, DSE_OP_Z, DSE_OP_P, DSE_OP_M, DSE_OP_EA, DSE_OP_EB = range(8)
 DSE_DIST_ID_BYTES = 128
 DSE_XCHG_ALLTOALL, DSE_XCHG_SENDRECV, DSE_XCHG_ALLREDUCE_F64 = 1, 2, 3
 # int fn(void* user, int op, void* send, void* recv, uint64_t bytes, int peer)
@@ -95,6 +100,7 @@ _lib = None
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
+_u8p = C.POINTER(C.c_uint8)
 
 
 def _declare(lib):
@@ -150,6 +156,13 @@ def _declare(lib):
         "dse_pulse_stats": (C.c_int, [_vp, _dp]),
         "dse_pulse_plan": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_int32)]),
         "dse_set_hamiltonian": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, C.c_double]),
+        "dse_set_op_strings": (C.c_int, [_vp, C.c_int, C.c_int, _u8p]),
+        "dse_op_strings": (C.c_int, [_vp, C.c_int]),
+        "dse_op_string_values": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+        "dse_get_op_strings": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_op_string_outputs": (C.c_int, [_vp]),
+        "dse_op_string_problems": (C.c_int, [_vp]),
+        "dse_op_string_masks": (C.c_int, [C.c_int, _u8p, C.POINTER(C.c_uint64), _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -179,6 +192,8 @@ def lib():
                 raise ImportError("libdse.so predates the overlaps with reference states; rebuild it")
             if not hasattr(handle, "dse_apply_pulse"):
                 raise ImportError("libdse.so predates the hard pulses (dse_apply_pulse); rebuild it")
+            if not hasattr(handle, "dse_set_op_strings"):
+                raise ImportError("libdse.so predates the operator strings (dse_set_op_strings); rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
@@ -188,10 +203,30 @@ def lib():
 
 def has_feature(name: str) -> bool:
     """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs",
-    "overlap_obs", "pulse", "set_hamiltonian")."""
+    "overlap_obs", "pulse", "set_hamiltonian", "op_strings")."""
     return bool(lib().dse_has_feature(name.encode()))
 
 
 def ptr(a):
     """double* of a contiguous float64/complex128 numpy array."""
     return a.ctypes.data_as(_dp)
+
+
+def u8ptr(a):
+    """uint8_t* of a contiguous uint8 numpy array."""
+    return a.ctypes.data_as(_u8p)
+
+
+def op_string_masks(ops):
+    """dse_op_string_masks: the compiled form of one operator string, codes by register bit:
+    ``(xm, zm, cm, cv, pre)`` with ``pre`` complex.  Host only."""
+    import numpy as np
+
+    o = np.ascontiguousarray(ops, dtype=np.uint8)
+    if o.ndim != 1:
+        raise ValueError("ops must be one string: a 1-D array of codes by register bit")
+    masks = (C.c_uint64 * 4)()
+    pre = (C.c_double * 2)()
+    if lib().dse_op_string_masks(int(o.size), u8ptr(o), masks, pre) != 0:
+        raise ValueError("dse_op_string_masks: 1..34 codes in 0..7 expected")
+    return int(masks[0]), int(masks[1]), int(masks[2]), int(masks[3]), complex(pre[0], pre[1])

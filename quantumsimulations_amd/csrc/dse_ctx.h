@@ -101,6 +101,13 @@ struct HostProblem {
   std::vector<double2*> ovl_refs;
   const double2** d_ovl_tab = nullptr;
   int ovl_k() const { return (int)ovl_refs.size(); }
+  // operator strings (dse_set_op_strings; every shard of a loopback register alike): the compiled
+  // table, masks by register bit, and its device copy the kernels read.  They belong to the problem
+  // like the references: kept over evolves, over free_device and over dse_set_hamiltonian, replaced
+  // as a set, released by dse_clear / dse_destroy
+  std::vector<StringEntry> str_tab;
+  StringEntry* d_str_tab = nullptr;
+  int str_k() const { return (int)str_tab.size(); }
 };
 
 inline int fail(dse_ctx* c, int code, const std::string& msg);
@@ -132,19 +139,20 @@ template <class... B>
 void release_all(B&... b) { (b.release(), ...); }
 
 // The observable families beside the seven aggregates: sums per unit (register bit, pair of bits,
-// reference state) of every output state, kept per register and read back after the evolve.
+// reference state, operator string) of every output state, kept per register and read back after the evolve.
 // kObsFamilies below describes each; the engines launch them in this order and read them back in the
 // reverse one.
-enum ObsFamily { kSite = 0, kPair = 1, kOverlap = 2, kNumObsFamilies = 3 };
-constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair, kOverlap};
-constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kOverlap, kPair, kSite};
+enum ObsFamily { kSite = 0, kPair = 1, kOverlap = 2, kString = 3, kNumObsFamilies = 4 };
+constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair, kOverlap, kString};
+constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kString, kOverlap, kPair, kSite};
 
 // What a context holds for one family: its option, a partial arena for the tile engine's kernel
 // (S doubles per tile and slot: the family's stride of the context's widest register), and the
 // results of the last evolve, per register [comps][units][n_t] (loopback group: shard 0's entry)
 struct ObsFamilyState {
-  int on = 0;              // the option's value; kOverlap: the context holds references (set_overlap_on)
-  int kmax = 0;            // kOverlap: the most references any register of the context holds
+  int on = 0;              // the option's value; a family with per-problem units (kOverlap, kString): the
+                           // context holds references / strings (set_unit_families_on)
+  int kmax = 0;            // such a family: the most units (references, strings) any register of the context holds
   DevBuf<double> d_partial;
   size_t slots = 0;
   int S = 0;
@@ -401,12 +409,13 @@ struct Arena {
 // One family: raw sums v of a register, comps per unit at v[comps * u + c] and ||psi||^2 at
 // v[family_norm_at], `stride` doubles per state; results normalised by that norm (site, pair:
 // expectation values, sums / ||psi||^2) or by its square root (overlap: linear in psi).
-// The units of site and pair follow from the register's size; the overlap's belong to the problem
-// (its K references) and its stride to the context (K_max), so both are asked of those.
+// The units of site and pair follow from the register's size; the overlap's and the string's belong
+// to the problem (its K references, its K strings) and their strides to the context (K_max), so both
+// are asked of those.
 struct ObsFamilyDesc {
   const char *option, *hook, *noun;  // the option's and the hook's names, the family's word in messages
   int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index);
-              // overlap: Re, Im of <phi_k|psi>
+              // overlap: Re, Im of <phi_k|psi>; string: Re, Im of the string's sum
   int (*units)(const HostProblem& P);
   int (*stride)(const dse_ctx* ctx, int n);  // of an n-qubit register of ctx
   bool per_problem_units;  // the units are the problem's own count (0: no record) and ||psi||^2 is at
@@ -436,6 +445,10 @@ inline const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
     {"overlap references", "dse_overlaps", "overlap", 2, [](const HostProblem& P) { return P.ovl_k(); },
      [](const dse_ctx* ctx, int) { return overlap_stride(ctx->fam[kOverlap].kmax); }, true, true, kSmallOverlapStride,
      launch_obs_overlap, launch_dense_obs_overlap, launch_dense_obs_overlap_c, &DenseProb::ovl, false, false, true},
+    // no option: on while the context holds strings (dse_set_op_strings)
+    {"operator strings", "dse_op_string_values", "string", 2, [](const HostProblem& P) { return P.str_k(); },
+     [](const dse_ctx* ctx, int) { return string_stride(ctx->fam[kString].kmax); }, true, false, kSmallStringStride,
+     launch_obs_strings, launch_dense_obs_strings, launch_dense_obs_strings_c, &DenseProb::strs, false, false, true},
 };
 inline int family_norm_at(const ObsFamilyDesc& F, int units, size_t stride) {
   return F.per_problem_units ? (int)stride - 2 : F.comps * units;

@@ -19,6 +19,8 @@
 #include <functional>
 #include <vector>
 
+#include "dse_internal.h"  // StringEntry
+
 namespace dse {
 
 constexpr int kDenseMaxQubits = 14;  // 2^14 x 2^14 fp64 = 2 GiB per eigenvector matrix
@@ -62,6 +64,10 @@ struct DenseProb {
   const double2* const* ovl_refs;
   int ovl_k;
   const double* tau;
+  // operator strings: strs [n_t][S] raw sums (k_dense_obs_strings), else null; the register's table
+  double* strs;
+  const StringEntry* str_tab;
+  int str_k;
 };
 
 // H' of every problem into its (zeroed) V
@@ -111,6 +117,13 @@ hipError_t launch_dense_obs_pairs_c(const DenseProb* d, int dim, const double* P
 hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
                                     int tb, int t0, int S, hipStream_t st);
 hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                      hipStream_t st);
+// operator strings of the registers' tables (dse_strings.hip): the raw sums of the same columns into
+// d[p].strs rows t0 .. t0 + tb of S = string_stride(K_max) doubles (Re, Im of string k at [2 k],
+// [2 k + 1], ||psi||^2 at [S - 2]); a register without strings is skipped; _c as above
+hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                    int tb, int t0, int S, hipStream_t st);
+hipError_t launch_dense_obs_strings_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
                                       hipStream_t st);
 // psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
 // the shift's phase exp(-i shift tau_last) included)

@@ -55,6 +55,17 @@ __host__ __device__ constexpr int pair_stride(int n) { return (5 * (n * (n - 1) 
 // most references any register of the context holds), zero elsewhere
 constexpr int kMaxOverlapRefs = 16;               // DSE_MAX_OVERLAP_REFS
 __host__ __device__ constexpr int overlap_stride(int kmax) { return 2 * kmax + 2; }
+// Operator strings (dse_strings.hip): a product of one-spin operators, one factor per register bit,
+// compiled on the host (dse_op_string_masks) into the masks of
+//   S = pre * sum_{x : (x & cm) == cv} (-1)^popcount(x & zm) conj(psi_x) psi_{x ^ xm}
+// Sums per register and state: Re, Im of S_k at [2 k], [2 k + 1] for k < K and ||psi||^2 at [S - 2],
+// S = string_stride(K_max) doubles per record, zero elsewhere
+constexpr int kMaxOpStrings = 64;                 // DSE_MAX_OP_STRINGS
+__host__ __device__ constexpr int string_stride(int kmax) { return 2 * kmax + 2; }
+struct StringEntry {
+  uint64_t xm, zm, cm, cv;  // flips, signs, selected bits and their required values in the row x
+  double pre_re, pre_im;
+};
 constexpr int kMaxShardBits = 3;                  // partitioned registers: up to 8 shards
 constexpr int kMaxShards = 1 << kMaxShardBits;
 // bits above an L-bit tile for the largest register (34 qubits), at least the 32-bit tile index
@@ -148,6 +159,10 @@ struct DevProb {
   // 2^n_local amplitudes each (null, 0: none)
   const double2* const* ovl_refs;
   int ovl_k;
+  // operator strings (dse_strings.hip): the register's compiled table of str_k entries, masks by
+  // register bit (every shard of a loopback register the same table; null, 0: none)
+  const StringEntry* str_tab;
+  int str_k;
 };
 
 // ---- spanning registers (dse_span.hip): one register over 2^s cooperating workgroups ----------
@@ -329,6 +344,12 @@ hipError_t launch_obs_pairs(int L, const DevProb* probs, const int2* items, int 
 // dse_overlap.hip): S = overlap_stride(K_max) doubles per tile, output j's partials at partial + j *
 // out_stride; the tiles of a register without references are left unwritten
 hipError_t launch_obs_overlap(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                              double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
+                              int xq = 0);
+// the operator strings of the registers' tables on the same outputs (k_obs_strings, dse_strings.hip):
+// S = string_stride(K_max) doubles per tile, output j's partials at partial + j * out_stride; the
+// tiles of a register without strings are left unwritten
+hipError_t launch_obs_strings(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                               double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                               int xq = 0);
 // partial[2 * block + {0, 1}] = block sums of Re(conj(a) b) and |a|^2 over n amplitudes

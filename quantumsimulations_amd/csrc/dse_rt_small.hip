@@ -78,6 +78,8 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     q.n_t = n_t;
     q.ovl_refs = P.d_ovl_tab;
     q.ovl_k = P.ovl_k();
+    q.str_tab = P.d_str_tab;
+    q.str_k = P.str_k();
     P.final_bsel = 0;
   }
   {
@@ -132,6 +134,10 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     if (int rc = ctx->fam[f].d_small.reserve(ctx, sn, what.c_str())) return rc;
     d_fam[f] = ctx->fam[f].d_small.p;
   }
+  // the string kernels (k_small_str, k_small_obs0_str) only when a small register of this call holds strings
+  bool sm_strings = false;
+  for (int pi : sm) sm_strings = sm_strings || ctx->probs[pi].str_k() > 0;
+  double* d_str = sm_strings ? d_fam[kString] : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
   if (int rc = ctx->d_small_out.reserve(ctx, outn, "small-engine output allocation failed")) return rc;
   // selections per register size, then the interval -> set map
@@ -149,14 +155,14 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
-                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair], d_fam[kOverlap]));
+                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair], d_fam[kOverlap], d_str));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
                         cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair],
-                        d_fam[kOverlap]));
+                        d_fam[kOverlap], d_str));
       *launches += 1.0;
     }
   }

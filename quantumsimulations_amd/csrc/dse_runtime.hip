@@ -146,6 +146,11 @@ void free_overlap_refs(HostProblem& p) {
   if (p.d_ovl_tab) (void)hipFree(p.d_ovl_tab), p.d_ovl_tab = nullptr;
 }
 
+void free_op_strings(HostProblem& p) {
+  p.str_tab.clear();
+  if (p.d_str_tab) (void)hipFree(p.d_str_tab), p.d_str_tab = nullptr;
+}
+
 void free_device(dse_ctx* ctx) {
   for (auto& p : ctx->probs) {
     for (auto& b : p.buf)
@@ -865,21 +870,27 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
 // ---- observable families: site-resolved observables and two-spin correlators ------------------
 
 
-// The overlap family has no option: it is on while any register of the context holds references,
-// and its stride follows the most any of them holds.  The references reach the kernels through the
-// descriptors: h_desc as dse_evolve uploads it, and with `upload` (the hook: no upload follows) the
-// device copy, every time (an evolve that failed before its upload leaves h_desc ahead of it).
-// After prepare.
-int set_overlap_on(dse_ctx* ctx, bool upload) {
-  int kmax = 0;
+// The overlap and string families have no option: each is on while any register of the context
+// holds references / strings, and its stride follows the most any of them holds.  Both reach the
+// kernels through the descriptors: h_desc as dse_evolve uploads it, and with `upload` (the hooks: no
+// upload follows) the device copy, every time (an evolve that failed before its upload leaves h_desc
+// ahead of it).  After prepare.
+int set_unit_families_on(dse_ctx* ctx, bool upload) {
+  int kmax[kNumObsFamilies] = {};
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
-    kmax = std::max(kmax, P.ovl_k());
+    for (ObsFamily f : kObsLaunchOrder)
+      if (kObsFamilies[f].per_problem_units) kmax[f] = std::max(kmax[f], kObsFamilies[f].units(P));
     ctx->h_desc[pi].ovl_refs = P.d_ovl_tab;
     ctx->h_desc[pi].ovl_k = P.ovl_k();
+    ctx->h_desc[pi].str_tab = P.d_str_tab;
+    ctx->h_desc[pi].str_k = P.str_k();
   }
-  ctx->fam[kOverlap].kmax = kmax;
-  ctx->fam[kOverlap].on = kmax > 0;
+  for (ObsFamily f : kObsLaunchOrder) {
+    if (!kObsFamilies[f].per_problem_units) continue;
+    ctx->fam[f].kmax = kmax[f];
+    ctx->fam[f].on = kmax[f] > 0;
+  }
   if (upload)
     HIPC(hipMemcpy(ctx->d_probs, ctx->h_desc.data(), ctx->h_desc.size() * sizeof(DevProb), hipMemcpyHostToDevice));
   return DSE_OK;
@@ -1280,7 +1291,7 @@ void dse_destroy(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p);
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p);
   ctx->d_mx.release();
   ctx->d_pulse_tab.release();
   for (auto& e : ctx->pulse_ev)
@@ -1520,7 +1531,7 @@ int dse_clear(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p);  // the initial states and references go with their problems
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p);  // the initial states, references and strings go with their problems
   ctx->probs.clear();
   return DSE_OK;
 }
@@ -1868,6 +1879,8 @@ int dense_fill_job(dse_ctx* ctx, const DenseRun& R, DenseJob& J) {
     D.ovl_refs = P.d_ovl_tab;
     D.ovl_k = P.ovl_k();
     D.tau = R.d_tau;
+    D.str_tab = P.d_str_tab;
+    D.str_k = P.str_k();
   }
   hipStream_t st = R.st;
   HIPC(hipMemcpyAsync(J.tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2398,6 +2411,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
     if (ctx->fam[f].on) D.*kObsFamilies[f].dense_out = reinterpret_cast<double*>(base + oFam[f]);
   D.ovl_refs = P.d_ovl_tab;  // (tau null: the states are in the computational frame, the shift's phase in U)
   D.ovl_k = P.ovl_k();
+  D.str_tab = P.d_str_tab;
+  D.str_k = P.str_k();
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
   std::vector<double> hfam[kNumObsFamilies];
@@ -2460,7 +2475,7 @@ int obs_family_hook(dse_ctx* ctx, ObsFamily f, int problem, const double* psi, d
   if (F.hook_refuses_shard_early && ctx->probs[first].dist)
     return fail(ctx, DSE_ERR_ARG, std::string(F.hook) + ": not available for a dist shard");
   HIPC(hipSetDevice(ctx->device));
-  if ((rc = prepare(ctx)) || (rc = set_overlap_on(ctx, true))) return rc;
+  if ((rc = prepare(ctx)) || (rc = set_unit_families_on(ctx, true))) return rc;
   if (!F.hook_refuses_shard_early && (rc = obs_family_refusal(ctx, f, F.hook))) return rc;
   if (F.per_problem_units && F.units(ctx->probs[first]) == 0)
     return fail(ctx, DSE_ERR_STATE, std::string(F.hook) + ": the problem has no " + F.option);
@@ -2583,11 +2598,16 @@ int dse_overlap_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kOverlap].nt
 int dse_overlap_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kOverlap) : DSE_ERR_ARG; }
 int dse_get_overlaps(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kOverlap, problem, out); }
 
+int dse_op_string_values(dse_ctx* ctx, int problem, const double* psi, double* out) { return obs_family_hook(ctx, kString, problem, psi, out); }
+int dse_op_string_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kString].nt : DSE_ERR_ARG; }
+int dse_op_string_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kString) : DSE_ERR_ARG; }
+int dse_get_op_strings(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kString, problem, out); }
+
 int dse_has_feature(const char* name) {
   if (!name) return 0;
   const std::string k(name);
   return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs" || k == "pulse" ||
-         k == "set_hamiltonian";
+         k == "set_hamiltonian" || k == "op_strings";
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -3915,7 +3935,7 @@ int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_
   ctx->xms = 0.0;
   ctx->xev_used = 0;
   pl.phase("prepare");
-  if ((rc = set_overlap_on(ctx, false)) || (rc = choose_engines(ctx, pl))) return rc;
+  if ((rc = set_unit_families_on(ctx, false)) || (rc = choose_engines(ctx, pl))) return rc;
   choose_span(ctx, pl);
   choose_real(ctx, pl);
   if ((rc = choose_wht(ctx, pl))) return rc;
@@ -4139,6 +4159,91 @@ int dse_overlap_refs(const dse_ctx* ctx, int problem) {
   return ctx->probs[problem].ovl_k();
 }
 
+// One string, codes by register bit, into its masks and prefactor (include/dse.h: dse_site_op).  With
+// bit value 0 = up: Ix = (|0><1| + |1><0|) / 2, Iy = (|0><1| - |1><0|) / 2i, Iz = diag(1, -1) / 2,
+// I+ = |0><1|, I- = |1><0|.  <x|O|x ^ flip> of one bit: Ix 1/2; Iy -i/2 for x = 0 and +i/2 for
+// x = 1, i.e. (-i/2) (-1)^x; Iz (1/2) (-1)^x; I+ only x = 0, I- only x = 1; Ea only x = 0, Eb only x = 1.
+bool compile_op_string(int n, const uint8_t* ops, StringEntry* e) {
+  StringEntry s{0, 0, 0, 0, 1.0, 0.0};
+  int halves = 0, ny = 0;
+  for (int b = 0; b < n; ++b) {
+    const uint64_t m = uint64_t(1) << b;
+    switch (ops[b]) {
+      case DSE_OP_1: break;
+      case DSE_OP_X: s.xm |= m, ++halves; break;
+      case DSE_OP_Y: s.xm |= m, s.zm |= m, ++halves, ++ny; break;
+      case DSE_OP_Z: s.zm |= m, ++halves; break;
+      case DSE_OP_P: s.xm |= m, s.cm |= m; break;
+      case DSE_OP_M: s.xm |= m, s.cm |= m, s.cv |= m; break;
+      case DSE_OP_EA: s.cm |= m; break;
+      case DSE_OP_EB: s.cm |= m, s.cv |= m; break;
+      default: return false;
+    }
+  }
+  const double mag = std::ldexp(1.0, -halves);
+  static const double kRe[4] = {1, 0, -1, 0}, kIm[4] = {0, -1, 0, 1};  // (-i)^k
+  s.pre_re = mag * kRe[ny & 3];
+  s.pre_im = mag * kIm[ny & 3];
+  *e = s;
+  return true;
+}
+
+int dse_op_string_masks(int n, const uint8_t* ops, uint64_t* masks, double* pre) {
+  if (n < 1 || n > DSE_MAX_QUBITS || !ops || !masks || !pre) return DSE_ERR_ARG;
+  StringEntry e;
+  if (!compile_op_string(n, ops, &e)) return DSE_ERR_ARG;
+  masks[0] = e.xm, masks[1] = e.zm, masks[2] = e.cm, masks[3] = e.cv;
+  pre[0] = e.pre_re, pre[1] = e.pre_im;
+  return DSE_OK;
+}
+
+int dse_set_op_strings(dse_ctx* ctx, int problem, int k, const uint8_t* ops) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_op_strings");
+  if (rc) return rc;
+  if (k < 0 || k > DSE_MAX_OP_STRINGS)
+    return fail(ctx, DSE_ERR_ARG, "dse_set_op_strings: k must be in 0.." + std::to_string(DSE_MAX_OP_STRINGS));
+  HIPC(hipSetDevice(ctx->device));
+  if (k == 0 || !ops) {
+    (void)sync_all(ctx);
+    for (int i = 0; i < count; ++i) free_op_strings(ctx->probs[first + i]);
+    return DSE_OK;
+  }
+  const int n = ctx->probs[first].n;
+  std::vector<StringEntry> tab(k);
+  for (int s = 0; s < k; ++s)
+    if (!compile_op_string(n, ops + (size_t)s * n, &tab[s]))
+      return fail(ctx, DSE_ERR_ARG, "dse_set_op_strings: string " + std::to_string(s) + " holds a code above 7");
+  // the new tables beside the old ones: a failed allocation leaves the previous set in place
+  std::vector<StringEntry*> fresh(count, nullptr);
+  hipError_t he = hipSuccess;
+  for (int i = 0; i < count && he == hipSuccess; ++i) {
+    he = hipMalloc(&fresh[i], tab.size() * sizeof(StringEntry));
+    if (he != hipSuccess) fresh[i] = nullptr;
+    if (he == hipSuccess) he = hipMemcpy(fresh[i], tab.data(), tab.size() * sizeof(StringEntry), hipMemcpyHostToDevice);
+  }
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    for (StringEntry* b : fresh)
+      if (b) (void)hipFree(b);
+    return fail(ctx, he == hipErrorOutOfMemory ? DSE_ERR_OOM : DSE_ERR_HIP, std::string("dse_set_op_strings: ") + hipGetErrorString(he));
+  }
+  (void)sync_all(ctx);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    free_op_strings(P);
+    P.str_tab = tab;
+    P.d_str_tab = fresh[i];
+  }
+  return DSE_OK;
+}
+
+int dse_op_strings(const dse_ctx* ctx, int problem) {
+  if (!ctx || problem < 0 || problem >= (int)ctx->probs.size()) return DSE_ERR_ARG;
+  return ctx->probs[problem].str_k();
+}
+
 int dse_set_initial_product(dse_ctx* ctx, int problem, const double* amp) {
   if (!ctx) return DSE_ERR_ARG;
   int first = 0, count = 1;
@@ -4325,6 +4430,7 @@ int dse_set_hamiltonian(dse_ctx* ctx, int problem, const double* field, const do
     f.init_kind = P.init_kind, f.init_state = P.init_state, f.d_init_amp = P.d_init_amp;
     f.init_amp = std::move(P.init_amp);
     f.ovl_refs = std::move(P.ovl_refs), f.d_ovl_tab = P.d_ovl_tab;
+    f.str_tab = std::move(P.str_tab), f.d_str_tab = P.d_str_tab;
     P = std::move(f);
   }
   return DSE_OK;

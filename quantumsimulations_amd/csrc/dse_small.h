@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "dse_internal.h"  // StringEntry
+
 namespace dse {
 
 constexpr int kSmallMaxQubits = 9;
@@ -18,6 +20,9 @@ constexpr int kSmallPairStride = 182;
 // overlaps with reference states per problem and output: Re, Im of <phi_k|psi> at [2 k], [2 k + 1],
 // ||psi||^2 at [32] (overlap_stride(16): every register's record is sized for the cap)
 constexpr int kSmallOverlapStride = 2 * 16 + 2;
+// operator strings per problem and output: Re, Im of string k at [2 k], [2 k + 1], ||psi||^2 at [128]
+// (string_stride(64): every register's record is sized for the cap)
+constexpr int kSmallStringStride = 2 * 64 + 2;
 
 struct SmallProb {
   double2* state;          // [2^n] the state at the start of the next launch
@@ -33,20 +38,26 @@ struct SmallProb {
   // the register's ovl_k reference states, 2^n amplitudes each (null, 0: none)
   const double2* const* ovl_refs;
   int ovl_k;
+  // the register's compiled operator strings (null, 0: none)
+  const StringEntry* str_tab;
+  int str_k;
 };
 
 // One launch: intervals m0 .. m0 + n_int - 1 of problems sel[0 .. count) (all with n qubits);
 // out[problem][m + 1][8] = raw observable sums of psi(t_{m+1}) (dse_runtime.hip finish_obs).
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
                         const int* iv_set, double* out, hipStream_t st, double* sites = nullptr,
-                        double* pairs = nullptr, double* ovl = nullptr);
+                        double* pairs = nullptr, double* ovl = nullptr, double* strs = nullptr);
 // out[problem][0][8] = observable sums of the state buffer (psi0)
 // sites non-null (both launches): also sites[problem][m][kSmallSiteStride], the site-resolved sums
 // pairs non-null (both launches): also pairs[problem][m][kSmallPairStride], the two-spin sums
 // ovl non-null (both launches): also ovl[problem][m][kSmallOverlapStride], the overlaps with the
 // problem's reference states (a problem without references: its records are left unwritten)
+// strs non-null (both launches): also strs[problem][m][kSmallStringStride], the operator strings of
+// the problem's table (a problem without strings: its records are left unwritten); the kernels are
+// then k_small_str / k_small_obs0_str, which take ovl and strs as run-time-optional pointers
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
                              hipStream_t st, double* sites = nullptr, double* pairs = nullptr,
-                             double* ovl = nullptr);
+                             double* ovl = nullptr, double* strs = nullptr);
 
 }  // namespace dse

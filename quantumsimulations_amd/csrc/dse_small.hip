@@ -157,10 +157,54 @@ __device__ __forceinline__ void small_overlap_sums(const double2* w, int lane, b
   }
 }
 
+// Operator strings of the state in LDS w (the record of dse_strings.hip at the stride
+// kSmallStringStride): strings in table order, the partner from LDS at x ^ xm, one wave butterfly per
+// sum, the prefactor applied when storing.  K = 0: nothing is written.
+template <int N>
+__device__ __forceinline__ void small_string_sums(const double2* w, int lane, bool live,
+                                                  const StringEntry* __restrict__ tab, int K, double* o) {
+  constexpr int R = SmallGeo<N>::R;
+  if (K <= 0) return;
+  double n2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double2 p = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
+    n2 += p.x * p.x + p.y * p.y;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+  for (int i = 2 * K + lane; i < kSmallStringStride; i += 64) o[i] = (i == kSmallStringStride - 2) ? n2 : 0.0;
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    const uint32_t xm = (uint32_t)tab[k].xm, zm = (uint32_t)tab[k].zm, cm = (uint32_t)tab[k].cm, cv = (uint32_t)tab[k].cv;
+    double re = 0.0, im = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const uint32_t x = (uint32_t)(r * 64 + lane);
+      if (!live || (x & cm) != cv) continue;
+      const double2 p = w[x], s = w[x ^ xm];
+      const double zr = p.x * s.x + p.y * s.y, zi = p.x * s.y - p.y * s.x;  // conj(p) s
+      const bool neg = __popc(x & zm) & 1;
+      re += neg ? -zr : zr;
+      im += neg ? -zi : zi;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      re += __shfl_xor(re, off, 64);
+      im += __shfl_xor(im, off, 64);
+    }
+    const double pr = tab[k].pre_re, pi = tab[k].pre_im;
+    if (lane < 2) o[2 * k + lane] = lane == 0 ? pr * re - pi * im : pr * im + pi * re;
+  }
+}
+
 #define DSE_SMALL_OVL 0
 #include "dse_small_kernels.inc"
 #undef DSE_SMALL_OVL
 #define DSE_SMALL_OVL 1
+#include "dse_small_kernels.inc"
+#undef DSE_SMALL_OVL
+#define DSE_SMALL_OVL 2
 #include "dse_small_kernels.inc"
 #undef DSE_SMALL_OVL
 
@@ -168,10 +212,13 @@ __device__ __forceinline__ void small_overlap_sums(const double2* w, int lane, b
 
 #define DSE_SMALL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
 
-// (SITES, PAIRS) of a launch from the two output pointers; with ovl the _ovl kernel of the same two
+// (SITES, PAIRS) of a launch from the two output pointers; with ovl the _ovl kernel of the same two,
+// with strs the _str kernel (ovl then optional at run time)
 #define DSE_SMALL_LAUNCH(K, q, S_, P_, ...)                                                                  \
   do {                                                                                                       \
-    if (ovl)                                                                                                 \
+    if (strs)                                                                                                \
+      hipLaunchKernelGGL((K##_str<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl, strs); \
+    else if (ovl)                                                                                               \
       hipLaunchKernelGGL((K##_ovl<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl); \
     else                                                                                                     \
       hipLaunchKernelGGL((K<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs);           \
@@ -190,7 +237,7 @@ __device__ __forceinline__ void small_overlap_sums(const double2* w, int lane, b
 
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
                         const int* iv_set, double* out, hipStream_t st, double* sites, double* pairs,
-                        double* ovl) {
+                        double* ovl, double* strs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
@@ -204,7 +251,7 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 }
 
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites, double* pairs, double* ovl) {
+                             hipStream_t st, double* sites, double* pairs, double* ovl, double* strs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \

@@ -41,6 +41,7 @@ __all__ = [
     "simulate_rare_pairs",
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
     "simulate_rare_from", "simulate_rare_sequence", "simulate_rare_overlaps", "rotation_matrices",
+    "simulate_rare_strings", "op_strings_by_bit", "rdm_strings", "rdm_from_string_values",
 ]
 
 _ENGINES: Dict[int, object] = {}
@@ -327,12 +328,13 @@ def _check_start(psi0, spins) -> None:
         raise ValueError("pass exactly one of psi0 and spins")
 
 
-def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng=None):
+def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng=None, ops_eng=None):
     """One evolve of the unreduced register of ``params`` from an engine-order ket or a product
     state; returns (t, obs dict, final state in engine order, the Problem).  ``refs_eng``: reference
     states of the register in engine order, (K, 2^n), or "initial" (the state the evolve starts
     from, as the engine holds it); the overlap traces (K, n_t) are then returned as a fifth item.
-    The engine is left cleared, so without references."""
+    ``ops_eng``: operator strings of the register by bit, (K, n) codes; their traces (K, n_t) are then
+    returned as the last item.  The engine is left cleared, so without references and strings."""
     t = time_grid(params)
     prob = build_problem(params, order="engine", reduce=False)
     eng.clear()
@@ -344,13 +346,18 @@ def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng
             eng.set_initial_product(pid, amps_by_site[prob.site_of_bit])
         if refs_eng is not None:
             eng.set_overlap_refs(pid, eng.initial_state(pid)[None, :] if isinstance(refs_eng, str) else refs_eng)
+        if ops_eng is not None:
+            eng.set_op_strings(pid, ops_eng)
         obs, _ = eng.evolve(t, tol=_tol())
         final = eng.state(pid)
         ovl = eng.overlap_traces(pid) if refs_eng is not None else None
+        strs = eng.op_string_traces(pid) if ops_eng is not None else None
     finally:
         eng.clear()
     out = (t, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}, final, prob)
-    return out if refs_eng is None else out + (ovl,)
+    if refs_eng is not None:
+        out = out + (ovl,)
+    return out if ops_eng is None else out + (strs,)
 
 
 def simulate_rare_from(params: DipolarRareParams, psi0=None, spins=None, return_state: bool = False,
@@ -407,6 +414,106 @@ def simulate_rare_overlaps(params: DipolarRareParams, refs, psi0=None, spins=Non
     eng = _engine(_default_device() if device is None else device)
     t, obs, _, _, ovl = _evolve_from(eng, params, psi_eng, amps, refs_eng)
     return t, obs, ovl
+
+
+# The alphabet of an operator string, one letter per site: the codes of enum dse_site_op
+# (include/dse.h): 1, Ix, Iy, Iz, I+, I-, Ea = |up><up|, Eb = |down><down|
+OP_STRING_ALPHABET = "1xyz+-ab"
+MAX_OP_STRINGS = 64  # DSE_MAX_OP_STRINGS
+
+
+def op_strings_by_bit(strings, site_of_bit: np.ndarray) -> np.ndarray:
+    """Operator strings over the alphabet ``"1xyz+-ab"``, one letter per site in the reference's site
+    order (each of length n_sites = len(site_of_bit)), as the ``(K, n)`` uint8 code array by register
+    bit that Engine.set_op_strings takes: ``out[s, b] = code(strings[s][site_of_bit[b]])``."""
+    site_of_bit = np.asarray(site_of_bit, dtype=np.int64)
+    n = site_of_bit.size
+    if isinstance(strings, str):
+        strings = [strings]
+    strings = list(strings)
+    if sorted(site_of_bit.tolist()) != list(range(n)):
+        raise ValueError("site_of_bit must be a permutation of the sites")
+    out = np.zeros((len(strings), n), dtype=np.uint8)
+    for k, w in enumerate(strings):
+        if not isinstance(w, str) or len(w) != n:
+            raise ValueError(f"string {k} must be a str of {n} letters, one per site")
+        codes = [OP_STRING_ALPHABET.find(ch) for ch in w]
+        if min(codes) < 0:
+            raise ValueError(f"string {k} holds a letter outside {OP_STRING_ALPHABET!r}")
+        out[k] = np.asarray(codes, dtype=np.uint8)[site_of_bit]
+    return out
+
+
+def simulate_rare_strings(params: DipolarRareParams, strings, psi0=None, spins=None, device: int | None = None):
+    """simulate_rare_from that also returns expectation values of operator strings:
+    ``(t, obs, values)``, ``values[k, j] = <psi(t_j)| prod_s O_s |psi(t_j)> / <psi|psi>`` (complex128)
+    for ``strings[k]``, a str of n_sea + 1 letters over ``"1xyz+-ab"`` in the reference's site order
+    (1, Ix, Iy, Iz, I+, I-, |up><up|, |down><down|); K <= 64.  ``psi0`` / ``spins`` as in
+    simulate_rare_from (at most one); with neither the evolution starts from
+    ``initial_state_rare(params)``.  See rdm_strings / rdm_from_string_values for reduced density
+    matrices."""
+    if psi0 is not None and spins is not None:
+        raise ValueError("pass at most one of psi0 and spins")
+    n_sites = params.n_sea + 1
+    if isinstance(strings, str):
+        strings = [strings]
+    strings = list(strings)
+    if not 1 <= len(strings) <= MAX_OP_STRINGS:
+        raise ValueError(f"pass 1..{MAX_OP_STRINGS} strings")
+    prob = build_problem(params, order="engine", reduce=False)
+    if len(prob.site_of_bit) != n_sites:
+        raise ValueError("the unreduced register must hold every site")
+    ops = op_strings_by_bit(strings, prob.site_of_bit)
+    if psi0 is None and spins is None:
+        psi0 = initial_state_rare(params)
+    amps = spin_amplitudes(spins, n_sites) if spins is not None else None
+    psi_eng = reference_to_engine_state(psi0, prob.site_of_bit) if psi0 is not None else None
+    eng = _engine(_default_device() if device is None else device)
+    t, obs, _, _, vals = _evolve_from(eng, params, psi_eng, amps, ops_eng=ops)
+    return t, obs, vals
+
+
+def rdm_strings(sites, n_sites: int) -> List[str]:
+    """The 4^m - 1 strings over {1, x, y, z} on the m <= 3 distinct ``sites`` (identity elsewhere, the
+    all-identity string left out) whose values determine the reduced density matrix of those sites.
+    String c - 1, c = 1 .. 4^m - 1, carries the letter ``"1xyz"[d_i]`` on ``sites[i]``, d the base-4
+    digits of c with ``sites[0]`` the most significant."""
+    sites = [int(x) for x in sites]
+    m = len(sites)
+    if not 1 <= m <= 3 or len(set(sites)) != m or min(sites) < 0 or max(sites) >= n_sites:
+        raise ValueError("sites: 1 to 3 distinct sites in 0..n_sites - 1")
+    out = []
+    for c in range(1, 4 ** m):
+        w = ["1"] * n_sites
+        for i, site in enumerate(sites):
+            w[site] = "1xyz"[(c >> (2 * (m - 1 - i))) & 3]
+        out.append("".join(w))
+    return out
+
+
+def rdm_from_string_values(values) -> np.ndarray:
+    """``(n_t, 2^m, 2^m)`` reduced density matrices from the values ``(4^m - 1, n_t)`` (or
+    ``(4^m - 1,)``: one time) of rdm_strings, rho = 2^-m sum_c <sigma_c> sigma_c with sigma = 2 I and
+    <sigma_0> = 1.  Basis: ``sites[0]`` the most significant bit, 0 = up.  The values of Hermitian
+    strings are real; their real parts are used, so rho is Hermitian with trace 1."""
+    v = np.asarray(values)
+    if v.ndim == 1:
+        v = v[:, None]
+    m = {3: 1, 15: 2, 63: 3}.get(v.shape[0]) if v.ndim == 2 else None
+    if m is None:
+        raise ValueError("values must have 4^m - 1 rows, m = 1, 2 or 3")
+    sig = np.array([[[1, 0], [0, 1]], [[0, 1], [1, 0]], [[0, -1j], [1j, 0]], [[1, 0], [0, -1]]], dtype=np.complex128)
+    dim = 1 << m
+    rho = np.zeros((v.shape[1], dim, dim), dtype=np.complex128)
+    rho += np.eye(dim) / dim
+    for c in range(1, 4 ** m):
+        digits = [(c >> (2 * (m - 1 - i))) & 3 for i in range(m)]
+        mat = np.ones((1, 1), dtype=np.complex128)
+        for d in digits:
+            mat = np.kron(mat, sig[d])
+        weight = sum(1 for d in digits if d)
+        rho += (v[c - 1].real * (2.0 ** weight / dim))[:, None, None] * mat[None]
+    return rho
 
 
 def rotation_matrices(vecs) -> np.ndarray:

@@ -342,6 +342,58 @@ class Engine:
         """Registers whose overlaps the last successful evolve produced."""
         return int(self._L.dse_overlap_problems(self._h))
 
+    # -- expectation values of operator strings (include/dse.h, feature "op_strings") --
+    def set_op_strings(self, pid: int, ops) -> None:
+        """Register ``pid`` carries the operator strings ``ops``: a ``(K, n)`` uint8 array,
+        ``ops[s, b]`` the code of register bit b in string s (0..7: 1, Ix, Iy, Iz, I+, I-, Ea, Eb;
+        K <= DSE_MAX_OP_STRINGS; a loopback partitioned register: shard 0's id and all n bits).  Every
+        later evolve keeps <psi(t_j)| prod_b O_b |psi(t_j)> / <psi|psi> of every output.  The set
+        replaces the previous one; ``None`` or an empty array clears it."""
+        pid = self._pid(pid)
+        if ops is None or len(ops) == 0:
+            self._check(self._L.dse_set_op_strings(self._h, pid, 0, None))
+            return
+        n = self.problems[pid].n_qubits
+        x = np.asarray(ops)
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.ndim != 2 or x.shape[1] != n:
+            raise ValueError(f"operator strings must have shape (K, {n})")
+        if not np.issubdtype(x.dtype, np.integer) or x.min() < 0 or x.max() > 255:
+            raise ValueError("operator codes must be integers in 0..7")
+        x = np.ascontiguousarray(x, dtype=np.uint8)
+        self._check(self._L.dse_set_op_strings(self._h, pid, x.shape[0], _lib.u8ptr(x)))
+
+    def op_strings(self, pid: int) -> int:
+        """K of register ``pid`` (0: none)."""
+        return self._check(self._L.dse_op_strings(self._h, self._pid(pid)))
+
+    def op_string_values(self, pid: int, psi: np.ndarray) -> np.ndarray:
+        """(K,) complex: the values of the register's strings on the given state
+        (dse_op_string_values: the tile kernel of the evolve).  RuntimeError for a register without
+        strings."""
+        pid = self._pid(pid)
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        out = np.empty((2, max(self.op_strings(pid), 1)))
+        self._check(self._L.dse_op_string_values(self._h, pid, _lib.ptr(x), _lib.ptr(out)))
+        return out[0] + 1j * out[1]
+
+    def op_string_traces(self, pid: int) -> np.ndarray:
+        """(K, n_t) complex128: the values of the register's strings at every output of the last
+        evolve (RuntimeError before one, after a failed one and for a register without strings)."""
+        pid = self._pid(pid)
+        n_t = max(int(self._L.dse_op_string_outputs(self._h)), 0)
+        out = np.empty((2, max(self.op_strings(pid), 1), max(n_t, 1)))
+        self._check(self._L.dse_get_op_strings(self._h, pid, _lib.ptr(out)))
+        return out[0] + 1j * out[1]
+
+    def op_string_problems(self) -> int:
+        """Registers whose string values the last successful evolve produced."""
+        return int(self._L.dse_op_string_problems(self._h))
+
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
         self._check(self._L.dse_get_state(self._h, pid, _lib.ptr(out)))
@@ -413,7 +465,7 @@ class Engine:
 
     def set_hamiltonian(self, pid: int, prob: Problem) -> None:
         """Register ``pid`` gets the tables of ``prob`` (the same number of qubits); it keeps its
-        initial state, overlap references, masks and shard layout.  The final state of the last evolve
+        initial state, overlap references, operator strings, masks and shard layout.  The final state of the last evolve
         is dropped: call continue_from_final first (dse_set_hamiltonian)."""
         pid = self._pid(pid)
         if prob.n_qubits != self.problems[pid].n_qubits:
