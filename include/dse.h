@@ -47,12 +47,14 @@ extern "C" {
  * a caller discovers them by name with dse_has_feature, and what would have been a stats counter is
  * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems; the overlaps with
  * reference states: feature "overlap_obs", dse_overlap_problems; the operator strings: feature
- * "op_strings", dse_op_string_problems). */
+ * "op_strings", dse_op_string_problems; the sector populations: feature "sector_obs",
+ * dse_sector_problems). */
 #define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
 #define DSE_MAX_OVERLAP_REFS 16 /* reference states per problem (dse_set_overlap_refs) */
 #define DSE_MAX_OP_STRINGS 64   /* operator strings per problem (dse_set_op_strings) */
+#define DSE_MAX_SECTOR_SETS 16  /* sector sets per problem (dse_set_sectors) */
 
 enum dse_status {
   DSE_OK = 0,
@@ -520,8 +522,58 @@ int dse_op_string_problems(const dse_ctx* ctx);
  * (1/2)^(#Ix + #Iy + #Iz) (-i)^#Iy.  DSE_ERR_ARG for n outside 1..DSE_MAX_QUBITS, a null pointer or a
  * code above 7. */
 int dse_op_string_masks(int n, const uint8_t* ops, uint64_t* masks, double* pre);
+/* ---- magnetisation-sector populations (feature "sector_obs") ----------------------------------
+ * The distribution of a state over the sectors of a total spin projection.  A sector set is three
+ * masks over register bits (bit value 0 = up): m the counted bits, cm the selecting bits, cv their
+ * required values; m & cm == 0 and cv & ~cm == 0, m == 0 is allowed.  Its B = popcount(m) + 1 values
+ * on a state psi are
+ *     P_j = sum_{x : (x & cm) == cv, popcount(x & m) == j} |psi_x|^2 / <psi|psi>,   j = 0 .. popcount(m)
+ * (j spins of m down): the full counting statistics of the polarisation of the spins m, whose mean
+ * is popcount(m)/2 - sum_b <Iz_b> and whose second moment the Iz Iz correlators give; the norm is the
+ * whole state's, so the bins of a set with a selection sum to the selection's probability.  For a pure
+ * state the multiple-quantum-coherence intensities follow from them: I_q = sum_M P_M P_{M-q}.
+ * A problem may carry K <= DSE_MAX_SECTOR_SETS sets; every dse_evolve then also keeps the U = sum_k B_k
+ * values of every output time, the bins of set 0, then set 1, ....
+ *   - The sets belong to the problem as the operator strings do: kept over repeated evolves and over
+ *     dse_set_hamiltonian, replaced as a set, dropped by dse_clear.  Storage: one table of 32 K bytes
+ *     per register (per shard of a loopback register).
+ *   - With no sets in the context nothing is allocated and no kernel is added; with them every other
+ *     result is bitwise what it is without, and no engine choice reads them.  Registers of one context
+ *     may hold different K, 0 included.
+ *   - Costs one more read of the state per output and an arena of U_max + 2 doubles per tile and
+ *     output slot.  No atomics: two runs give bitwise equal values.
+ *   - dse_evolve returns DSE_ERR_ARG before any work for a context that holds both sets and a
+ *     register partitioned over processes (shard_rank >= 0). */
+/* Host only: validation and layout of k sets on an n-bit register.  masks: [k][3], m, cm, cv of set
+ * s at masks[3 s .. 3 s + 2].  Returns U and, with offsets non-null, offsets[s] the first unit of set
+ * s and offsets[k] = U.  DSE_ERR_ARG for n outside 1..DSE_MAX_QUBITS, k outside
+ * 1..DSE_MAX_SECTOR_SETS, a mask bit at or above n, m & cm != 0, cv & ~cm != 0 and null masks. */
+int dse_sector_layout(int n, int k, const uint64_t* masks, int* offsets);
+/* masks as above (bits are register bits); k = 0 drops the sets.  DSE_ERR_ARG for a bad id, a
+ * non-zero shard id of a loopback register (shard 0's id, masks over all n bits), a register
+ * partitioned over processes and whatever dse_sector_layout refuses; a failed allocation leaves the
+ * previous sets in place. */
+int dse_set_sectors(dse_ctx* ctx, int problem, int k, const uint64_t* masks);
+/* K of the problem (0: none), or DSE_ERR_ARG for a bad id. */
+int dse_sectors(const dse_ctx* ctx, int problem);
+/* U of the problem (0: none), or DSE_ERR_ARG for a bad id. */
+int dse_sector_units(const dse_ctx* ctx, int problem);
+/* The values of the problem's sets on an arbitrary state psi (2^n interleaved complex): out[U] (the
+ * hook beside dse_op_string_values; runs the tile kernel of the evolve; DSE_ERR_STATE for a problem
+ * without sets). */
+int dse_sector_values(dse_ctx* ctx, int problem, const double* psi, double* out);
+/* After dse_evolve: out[U][n_t] (a loopback partitioned register: shard 0's id).  The lifetime rules
+ * of dse_get_op_strings: DSE_ERR_STATE before an evolve, for a problem without sets, and after any
+ * dse_evolve that did not return DSE_OK.  After the re-run that follows a hand-off timeout the
+ * results are the re-run's (the dense engine's registers keep their first-pass results). */
+int dse_get_sectors(dse_ctx* ctx, int problem, double* out);
+/* n_t of the results dse_get_sectors would return, 0 when there are none. */
+int dse_sector_outputs(const dse_ctx* ctx);
+/* Registers whose sector populations the last successful dse_evolve produced (a loopback partitioned
+ * register counts once), 0 when there are none. */
+int dse_sector_problems(const dse_ctx* ctx);
 /* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
- * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian", "op_strings". */
+ * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs". */
 int dse_has_feature(const char* name);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);

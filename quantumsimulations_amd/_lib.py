@@ -39,9 +39,12 @@ EXPORTED = (
     "dse_apply_pulse", "dse_pulse_stats", "dse_pulse_plan", "dse_set_hamiltonian",
     "dse_set_op_strings", "dse_op_strings", "dse_op_string_values", "dse_get_op_strings",
     "dse_op_string_outputs", "dse_op_string_problems", "dse_op_string_masks",
+    "dse_sector_layout", "dse_set_sectors", "dse_sectors", "dse_sector_units", "dse_sector_values",
+    "dse_get_sectors", "dse_sector_outputs", "dse_sector_problems",
 )
 DSE_MAX_OVERLAP_REFS = 16
 DSE_MAX_OP_STRINGS = 64
+DSE_MAX_SECTOR_SETS = 16
 # enum dse_site_op: the code of a register bit in an operator string
 DSE_OP_1, DSE_OP_X, DSE_OP_Y, DSE_OP_Z, DSE_OP_P, DSE_OP_M, DSE_OP_EA, DSE_OP_EB = range(8)
 DSE_DIST_ID_BYTES = 128
@@ -101,6 +104,7 @@ _lib = None
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
 
 
 def _declare(lib):
@@ -163,6 +167,14 @@ def _declare(lib):
         "dse_op_string_outputs": (C.c_int, [_vp]),
         "dse_op_string_problems": (C.c_int, [_vp]),
         "dse_op_string_masks": (C.c_int, [C.c_int, _u8p, C.POINTER(C.c_uint64), _dp]),
+        "dse_sector_layout": (C.c_int, [C.c_int, C.c_int, _u64p, C.POINTER(C.c_int)]),
+        "dse_set_sectors": (C.c_int, [_vp, C.c_int, C.c_int, _u64p]),
+        "dse_sectors": (C.c_int, [_vp, C.c_int]),
+        "dse_sector_units": (C.c_int, [_vp, C.c_int]),
+        "dse_sector_values": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+        "dse_get_sectors": (C.c_int, [_vp, C.c_int, _dp]),
+        "dse_sector_outputs": (C.c_int, [_vp]),
+        "dse_sector_problems": (C.c_int, [_vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -194,6 +206,8 @@ def lib():
                 raise ImportError("libdse.so predates the hard pulses (dse_apply_pulse); rebuild it")
             if not hasattr(handle, "dse_set_op_strings"):
                 raise ImportError("libdse.so predates the operator strings (dse_set_op_strings); rebuild it")
+            if not hasattr(handle, "dse_set_sectors"):
+                raise ImportError("libdse.so predates the sector populations (dse_set_sectors); rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
@@ -203,7 +217,7 @@ def lib():
 
 def has_feature(name: str) -> bool:
     """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs",
-    "overlap_obs", "pulse", "set_hamiltonian", "op_strings")."""
+    "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs")."""
     return bool(lib().dse_has_feature(name.encode()))
 
 
@@ -230,3 +244,36 @@ def op_string_masks(ops):
     if lib().dse_op_string_masks(int(o.size), u8ptr(o), masks, pre) != 0:
         raise ValueError("dse_op_string_masks: 1..34 codes in 0..7 expected")
     return int(masks[0]), int(masks[1]), int(masks[2]), int(masks[3]), complex(pre[0], pre[1])
+
+
+def u64ptr(a):
+    """uint64_t* of a contiguous uint64 numpy array."""
+    return a.ctypes.data_as(_u64p)
+
+
+def sector_masks(masks, what: str = "sector masks"):
+    """``masks`` as the contiguous ``(K, 3)`` uint64 array (m, cm, cv per set) the library takes; one
+    set may be given as three numbers."""
+    import numpy as np
+
+    try:
+        rows = [[int(v) for v in row] for row in (np.asarray(masks, dtype=object).reshape(-1, 3).tolist())]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must have shape (K, 3): m, cm, cv per set") from None
+    if any(v < 0 or v >= 1 << 64 for row in rows for v in row):
+        raise ValueError(f"{what} must be non-negative 64-bit integers")
+    return np.array(rows, dtype=np.uint64).reshape(-1, 3)
+
+
+def sector_layout(n: int, masks):
+    """dse_sector_layout: ``(U, offsets)`` of the sets ``masks`` (``(K, 3)``: m, cm, cv) on an n-bit
+    register; ``offsets`` is the ``(K + 1,)`` int array of each set's first unit, ``offsets[K] = U``.
+    ValueError for what the library refuses.  Host only."""
+    import numpy as np
+
+    x = sector_masks(masks)
+    off = (C.c_int * (x.shape[0] + 1))()
+    u = lib().dse_sector_layout(int(n), int(x.shape[0]), u64ptr(x), off)
+    if u < 0:
+        raise ValueError("dse_sector_layout: n in 1..34, 1..16 sets, bits below n, m & cm == 0 and cv within cm expected")
+    return int(u), np.array(off[:], dtype=np.int64)

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdse.so")
-SOURCES = ["dse_kernels.hip", "dse_interval.hip", "dse_wht.hip", "dse_small.hip", "dse_dense.hip", "dse_pairs.hip", "dse_overlap.hip", "dse_strings.hip",
+SOURCES = ["dse_kernels.hip", "dse_interval.hip", "dse_wht.hip", "dse_small.hip", "dse_dense.hip", "dse_pairs.hip", "dse_overlap.hip", "dse_strings.hip", "dse_sectors.hip",
            "dse_matrix.hip", "dse_sytrd.hip", "dse_eig2.hip", "dse_span.hip", "dse_real.hip", "dse_nufft.hip",
            "dse_init.hip", "dse_pulse.hip", "dse_runtime.hip", "dse_rt_small.hip", "dse_host.cpp"]
 HEADERS = ["dse_internal.h", "dse_device.h", "dse_wht.h", "dse_small.h", "dse_dense.h", "dse_ctx.h", "dse_small_kernels.inc"]

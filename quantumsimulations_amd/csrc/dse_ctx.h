@@ -108,6 +108,13 @@ struct HostProblem {
   std::vector<StringEntry> str_tab;
   StringEntry* d_str_tab = nullptr;
   int str_k() const { return (int)str_tab.size(); }
+  // sector sets (dse_set_sectors; every shard of a loopback register alike): the table, masks by
+  // register bit with each set's first unit, and its device copy.  They belong to the problem as the
+  // strings do
+  std::vector<SectorEntry> sec_tab;
+  SectorEntry* d_sec_tab = nullptr;
+  int sec_k() const { return (int)sec_tab.size(); }
+  int sec_units() const { return sec_tab.empty() ? 0 : sec_tab.back().off + sec_tab.back().bins; }
 };
 
 inline int fail(dse_ctx* c, int code, const std::string& msg);
@@ -139,20 +146,20 @@ template <class... B>
 void release_all(B&... b) { (b.release(), ...); }
 
 // The observable families beside the seven aggregates: sums per unit (register bit, pair of bits,
-// reference state, operator string) of every output state, kept per register and read back after the evolve.
+// reference state, operator string, sector bin) of every output state, kept per register and read back after the evolve.
 // kObsFamilies below describes each; the engines launch them in this order and read them back in the
 // reverse one.
-enum ObsFamily { kSite = 0, kPair = 1, kOverlap = 2, kString = 3, kNumObsFamilies = 4 };
-constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair, kOverlap, kString};
-constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kString, kOverlap, kPair, kSite};
+enum ObsFamily { kSite = 0, kPair = 1, kOverlap = 2, kString = 3, kSector = 4, kNumObsFamilies = 5 };
+constexpr ObsFamily kObsLaunchOrder[kNumObsFamilies] = {kSite, kPair, kOverlap, kString, kSector};
+constexpr ObsFamily kObsReadbackOrder[kNumObsFamilies] = {kSector, kString, kOverlap, kPair, kSite};
 
 // What a context holds for one family: its option, a partial arena for the tile engine's kernel
 // (S doubles per tile and slot: the family's stride of the context's widest register), and the
 // results of the last evolve, per register [comps][units][n_t] (loopback group: shard 0's entry)
 struct ObsFamilyState {
-  int on = 0;              // the option's value; a family with per-problem units (kOverlap, kString): the
-                           // context holds references / strings (set_unit_families_on)
-  int kmax = 0;            // such a family: the most units (references, strings) any register of the context holds
+  int on = 0;              // the option's value; a family with per-problem units (kOverlap, kString, kSector):
+                           // the context holds references / strings / sets (set_unit_families_on)
+  int kmax = 0;            // such a family: the most units (references, strings, bins) any register of the context holds
   DevBuf<double> d_partial;
   size_t slots = 0;
   int S = 0;
@@ -409,13 +416,13 @@ struct Arena {
 // One family: raw sums v of a register, comps per unit at v[comps * u + c] and ||psi||^2 at
 // v[family_norm_at], `stride` doubles per state; results normalised by that norm (site, pair:
 // expectation values, sums / ||psi||^2) or by its square root (overlap: linear in psi).
-// The units of site and pair follow from the register's size; the overlap's and the string's belong
-// to the problem (its K references, its K strings) and their strides to the context (K_max), so both
-// are asked of those.
+// The units of site and pair follow from the register's size; the overlap's, the string's and the
+// sector's belong to the problem (its K references, its K strings, the U bins of its sets) and their
+// strides to the context (K_max, U_max), so both are asked of those.
 struct ObsFamilyDesc {
   const char *option, *hook, *noun;  // the option's and the hook's names, the family's word in messages
   int comps;  // site: X Y Z of a bit; pair: ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of a pair (pair_index);
-              // overlap: Re, Im of <phi_k|psi>; string: Re, Im of the string's sum
+              // overlap: Re, Im of <phi_k|psi>; string: Re, Im of the string's sum; sector: the bin
   int (*units)(const HostProblem& P);
   int (*stride)(const dse_ctx* ctx, int n);  // of an n-qubit register of ctx
   bool per_problem_units;  // the units are the problem's own count (0: no record) and ||psi||^2 is at
@@ -449,6 +456,10 @@ inline const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
     {"operator strings", "dse_op_string_values", "string", 2, [](const HostProblem& P) { return P.str_k(); },
      [](const dse_ctx* ctx, int) { return string_stride(ctx->fam[kString].kmax); }, true, false, kSmallStringStride,
      launch_obs_strings, launch_dense_obs_strings, launch_dense_obs_strings_c, &DenseProb::strs, false, false, true},
+    // no option: on while the context holds sector sets (dse_set_sectors); a unit is one bin
+    {"sector sets", "dse_sector_values", "sector", 1, [](const HostProblem& P) { return P.sec_units(); },
+     [](const dse_ctx* ctx, int) { return sector_stride(ctx->fam[kSector].kmax); }, true, false, kSmallSectorStride,
+     launch_obs_sectors, launch_dense_obs_sectors, launch_dense_obs_sectors_c, &DenseProb::secs, false, false, true},
 };
 inline int family_norm_at(const ObsFamilyDesc& F, int units, size_t stride) {
   return F.per_problem_units ? (int)stride - 2 : F.comps * units;

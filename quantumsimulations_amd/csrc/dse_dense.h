@@ -68,6 +68,10 @@ struct DenseProb {
   double* strs;
   const StringEntry* str_tab;
   int str_k;
+  // sector sets: secs [n_t][S] raw sums (k_dense_obs_sectors), else null; the register's table
+  double* secs;
+  const SectorEntry* sec_tab;
+  int sec_k;
 };
 
 // H' of every problem into its (zeroed) V
@@ -124,6 +128,13 @@ hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double*
 hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
                                     int tb, int t0, int S, hipStream_t st);
 hipError_t launch_dense_obs_strings_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
+                                      hipStream_t st);
+// sector populations of the registers' sets (dse_sectors.hip): the raw sums of the same columns into
+// d[p].secs rows t0 .. t0 + tb of S = sector_stride(U_max) doubles (set k's bins from [off_k],
+// ||psi||^2 at [S - 2]); a register without sets is skipped; _c as above
+hipError_t launch_dense_obs_sectors(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
+                                    int tb, int t0, int S, hipStream_t st);
+hipError_t launch_dense_obs_sectors_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
                                       hipStream_t st);
 // psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
 // the shift's phase exp(-i shift tau_last) included)

@@ -25,6 +25,56 @@ __device__ __forceinline__ double2 cmad(double2 acc, double cr, double ci, doubl
 
 __device__ __forceinline__ int par32(uint32_t v) { return __popc(v) & 1; }
 
+// Sector bins of one wave (dse_sectors.hip, small_sector_sums): lane l holds q[r], the selected
+// |psi|^2 of its 2^LR rows; row bit s and lane bit b are counted when set in m_rows / m_lanes (both
+// uniform).  A vector of partial bins, indexed by the number of counted bits set so far, is merged
+// pairwise over the row bits and then over the six lane bits:
+//   new[c] = own[c] + (bit counted ? partner[c - 1] : partner[c])
+// with the partner the half whose bit is 1.  The length grows by one per step whether or not the bit
+// is counted, so every index is a compile-time constant and nothing is a run-time-indexed per-thread
+// array.  v[0 .. LR + 6] of lane 0 are the wave's bins (the other lanes hold sums of no use: at every
+// step only the lanes whose lower bits are clear feed lane 0, and those are always the 0 side).
+template <int LR>
+__device__ __forceinline__ void sector_wave_bins(const double (&q)[1 << LR], uint32_t m_rows, uint32_t m_lanes,
+                                                 double (&v)[LR + 7]) {
+  constexpr int R = 1 << LR;
+  double a[R][LR + 1];
+#pragma unroll
+  for (int r = 0; r < R; ++r) a[r][0] = q[r];
+#pragma unroll
+  for (int s = 0; s < LR; ++s) {
+    const bool cnt = (m_rows >> s) & 1u;
+#pragma unroll
+    for (int r = 0; r < R; r += 2 << s)
+#pragma unroll
+      for (int c = s + 1; c >= 0; --c) {
+        const double own = c <= s ? a[r][c] : 0.0;
+        const double same = c <= s ? a[r + (1 << s)][c] : 0.0;
+        const double up = c >= 1 ? a[r + (1 << s)][c - 1] : 0.0;
+        a[r][c] = own + (cnt ? up : same);
+      }
+  }
+#pragma unroll
+  for (int c = 0; c <= LR; ++c) v[c] = a[0][c];
+#pragma unroll
+  for (int b = 0; b < 6; ++b) {
+    const int len = LR + 1 + b;
+    const bool cnt = (m_lanes >> b) & 1u;
+    double t[LR + 7];
+#pragma unroll
+    for (int c = 0; c < LR + 7; ++c)
+      if (c < len) t[c] = __shfl_xor(v[c], 1 << b, 64);
+#pragma unroll
+    for (int c = LR + 6; c >= 0; --c) {
+      if (c > len) continue;
+      const double own = c < len ? v[c] : 0.0;
+      const double same = c < len ? t[c] : 0.0;
+      const double up = c >= 1 ? t[c - 1] : 0.0;
+      v[c] = own + (cnt ? up : same);
+    }
+  }
+}
+
 // constant address space: uniform loads become scalar loads (SGPRs, scalar cache)
 template <typename T>
 using cptr = const __attribute__((address_space(4))) T*;

@@ -66,6 +66,17 @@ struct StringEntry {
   uint64_t xm, zm, cm, cv;  // flips, signs, selected bits and their required values in the row x
   double pre_re, pre_im;
 };
+// Magnetisation-sector populations (dse_sectors.hip): a set is three masks over register bits, m the
+// counted bits, cm / cv the selecting bits and their values; its B = popcount(m) + 1 bins are
+//   bin_j = sum_{x : (x & cm) == cv, popcount(x & m) == j} |psi_x|^2.
+// Sums per register and state: the bins of set 0, then set 1, ... (set k's at [off_k + j]), U = sum_k B_k
+// in all, and ||psi||^2 at [S - 2], S = sector_stride(U_max) doubles per record, zero elsewhere
+constexpr int kMaxSectorSets = 16;                // DSE_MAX_SECTOR_SETS
+__host__ __device__ constexpr int sector_stride(int umax) { return umax + 2; }
+struct SectorEntry {
+  uint64_t m, cm, cv;  // counted bits, selecting bits and their required values
+  int off, bins;       // the set's first unit in the record, popcount(m) + 1
+};
 constexpr int kMaxShardBits = 3;                  // partitioned registers: up to 8 shards
 constexpr int kMaxShards = 1 << kMaxShardBits;
 // bits above an L-bit tile for the largest register (34 qubits), at least the 32-bit tile index
@@ -163,6 +174,10 @@ struct DevProb {
   // register bit (every shard of a loopback register the same table; null, 0: none)
   const StringEntry* str_tab;
   int str_k;
+  // sector sets (dse_sectors.hip): the register's table of sec_k entries, masks by register bit
+  // (every shard of a loopback register the same table; null, 0: none)
+  const SectorEntry* sec_tab;
+  int sec_k;
 };
 
 // ---- spanning registers (dse_span.hip): one register over 2^s cooperating workgroups ----------
@@ -350,6 +365,12 @@ hipError_t launch_obs_overlap(int L, const DevProb* probs, const int2* items, in
 // S = string_stride(K_max) doubles per tile, output j's partials at partial + j * out_stride; the
 // tiles of a register without strings are left unwritten
 hipError_t launch_obs_strings(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
+                              double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
+                              int xq = 0);
+// the sector populations of the registers' sets on the same outputs (k_obs_sectors, dse_sectors.hip):
+// S = sector_stride(U_max) doubles per tile, output j's partials at partial + j * out_stride; the
+// tiles of a register without sets are left unwritten
+hipError_t launch_obs_sectors(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                               double* partial, int S, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                               int xq = 0);
 // partial[2 * block + {0, 1}] = block sums of Re(conj(a) b) and |a|^2 over n amplitudes

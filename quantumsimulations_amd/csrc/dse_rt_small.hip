@@ -80,6 +80,8 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
     q.ovl_k = P.ovl_k();
     q.str_tab = P.d_str_tab;
     q.str_k = P.str_k();
+    q.sec_tab = P.d_sec_tab;
+    q.sec_k = P.sec_k();
     P.final_bsel = 0;
   }
   {
@@ -138,6 +140,10 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   bool sm_strings = false;
   for (int pi : sm) sm_strings = sm_strings || ctx->probs[pi].str_k() > 0;
   double* d_str = sm_strings ? d_fam[kString] : nullptr;
+  // the sector kernels (k_small_sec, k_small_obs0_sec) only when a small register of this call holds sets
+  bool sm_sectors = false;
+  for (int pi : sm) sm_sectors = sm_sectors || ctx->probs[pi].sec_k() > 0;
+  double* d_sec = sm_sectors ? d_fam[kSector] : nullptr;
   const size_t outn = ctx->probs.size() * (size_t)n_t * 8;
   if (int rc = ctx->d_small_out.reserve(ctx, outn, "small-engine output allocation failed")) return rc;
   // selections per register size, then the interval -> set map
@@ -155,14 +161,14 @@ int small_launch(dse_ctx* ctx, const double* t, int n_t, double tol, double* h_a
   hipStream_t st = ctx->small_stream;
   for (const auto& g : groups)
     HIPC(launch_small_obs0(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second,
-                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair], d_fam[kOverlap], d_str));
+                           ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair], d_fam[kOverlap], d_str, d_sec));
   const int chunk = std::max(1, ctx->small_chunk);
   for (int m0 = 0; m0 + 1 < n_t; m0 += chunk) {
     const int cnt = std::min(chunk, n_t - 1 - m0);
     for (const auto& g : groups) {
       HIPC(launch_small(g.first, ctx->d_small.p, ctx->d_small_aux.p + g.second.first, g.second.second, m0,
                         cnt, ctx->d_small_aux.p + iv_off, ctx->d_small_out.p, st, d_fam[kSite], d_fam[kPair],
-                        d_fam[kOverlap], d_str));
+                        d_fam[kOverlap], d_str, d_sec));
       *launches += 1.0;
     }
   }

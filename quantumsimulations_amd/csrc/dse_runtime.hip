@@ -151,6 +151,11 @@ void free_op_strings(HostProblem& p) {
   if (p.d_str_tab) (void)hipFree(p.d_str_tab), p.d_str_tab = nullptr;
 }
 
+void free_sectors(HostProblem& p) {
+  p.sec_tab.clear();
+  if (p.d_sec_tab) (void)hipFree(p.d_sec_tab), p.d_sec_tab = nullptr;
+}
+
 void free_device(dse_ctx* ctx) {
   for (auto& p : ctx->probs) {
     for (auto& b : p.buf)
@@ -870,8 +875,8 @@ int ensure_partial(dse_ctx* ctx, size_t slots) {
 // ---- observable families: site-resolved observables and two-spin correlators ------------------
 
 
-// The overlap and string families have no option: each is on while any register of the context
-// holds references / strings, and its stride follows the most any of them holds.  Both reach the
+// The overlap, string and sector families have no option: each is on while any register of the context
+// holds references / strings / sets, and its stride follows the most any of them holds.  All reach the
 // kernels through the descriptors: h_desc as dse_evolve uploads it, and with `upload` (the hooks: no
 // upload follows) the device copy, every time (an evolve that failed before its upload leaves h_desc
 // ahead of it).  After prepare.
@@ -885,6 +890,8 @@ int set_unit_families_on(dse_ctx* ctx, bool upload) {
     ctx->h_desc[pi].ovl_k = P.ovl_k();
     ctx->h_desc[pi].str_tab = P.d_str_tab;
     ctx->h_desc[pi].str_k = P.str_k();
+    ctx->h_desc[pi].sec_tab = P.d_sec_tab;
+    ctx->h_desc[pi].sec_k = P.sec_k();
   }
   for (ObsFamily f : kObsLaunchOrder) {
     if (!kObsFamilies[f].per_problem_units) continue;
@@ -1291,7 +1298,7 @@ void dse_destroy(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p);
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p), free_sectors(p);
   ctx->d_mx.release();
   ctx->d_pulse_tab.release();
   for (auto& e : ctx->pulse_ev)
@@ -1531,7 +1538,7 @@ int dse_clear(dse_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   (void)sync_all(ctx);
   free_device(ctx);
-  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p);  // the initial states, references and strings go with their problems
+  for (auto& p : ctx->probs) free_initial(p), free_overlap_refs(p), free_op_strings(p), free_sectors(p);  // the initial states, references, strings and sets go with their problems
   ctx->probs.clear();
   return DSE_OK;
 }
@@ -1881,6 +1888,8 @@ int dense_fill_job(dse_ctx* ctx, const DenseRun& R, DenseJob& J) {
     D.tau = R.d_tau;
     D.str_tab = P.d_str_tab;
     D.str_k = P.str_k();
+    D.sec_tab = P.d_sec_tab;
+    D.sec_k = P.sec_k();
   }
   hipStream_t st = R.st;
   HIPC(hipMemcpyAsync(J.tabs, htabs.data(), htabs.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -2413,6 +2422,8 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.ovl_k = P.ovl_k();
   D.str_tab = P.d_str_tab;
   D.str_k = P.str_k();
+  D.sec_tab = P.d_sec_tab;
+  D.sec_k = P.sec_k();
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
   HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
   std::vector<double> hfam[kNumObsFamilies];
@@ -2603,11 +2614,16 @@ int dse_op_string_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kString].n
 int dse_op_string_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kString) : DSE_ERR_ARG; }
 int dse_get_op_strings(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kString, problem, out); }
 
+int dse_sector_values(dse_ctx* ctx, int problem, const double* psi, double* out) { return obs_family_hook(ctx, kSector, problem, psi, out); }
+int dse_sector_outputs(const dse_ctx* ctx) { return ctx ? ctx->fam[kSector].nt : DSE_ERR_ARG; }
+int dse_sector_problems(const dse_ctx* ctx) { return ctx ? obs_family_problems(ctx, kSector) : DSE_ERR_ARG; }
+int dse_get_sectors(dse_ctx* ctx, int problem, double* out) { return obs_family_get(ctx, kSector, problem, out); }
+
 int dse_has_feature(const char* name) {
   if (!name) return 0;
   const std::string k(name);
   return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs" || k == "pulse" ||
-         k == "set_hamiltonian" || k == "op_strings";
+         k == "set_hamiltonian" || k == "op_strings" || k == "sector_obs";
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -4244,6 +4260,84 @@ int dse_op_strings(const dse_ctx* ctx, int problem) {
   return ctx->probs[problem].str_k();
 }
 
+// k sets of an n-bit register, masks[s] = {m, cm, cv}, into the table: validation and layout in one
+// place (dse_sector_layout, dse_set_sectors).  The units U, or -1 for what the header refuses.
+int compile_sectors(int n, int k, const uint64_t* masks, std::vector<SectorEntry>* tab) {
+  if (n < 1 || n > DSE_MAX_QUBITS || k < 1 || k > DSE_MAX_SECTOR_SETS || !masks) return -1;
+  const uint64_t all = n >= 64 ? ~uint64_t(0) : (uint64_t(1) << n) - 1;
+  int off = 0;
+  if (tab) tab->clear();
+  for (int s = 0; s < k; ++s) {
+    const uint64_t m = masks[3 * s], cm = masks[3 * s + 1], cv = masks[3 * s + 2];
+    if (((m | cm | cv) & ~all) || (m & cm) || (cv & ~cm)) return -1;
+    const int bins = __builtin_popcountll(m) + 1;
+    if (tab) tab->push_back(SectorEntry{m, cm, cv, off, bins});
+    off += bins;
+  }
+  return off;
+}
+
+int dse_sector_layout(int n, int k, const uint64_t* masks, int* offsets) {
+  std::vector<SectorEntry> tab;
+  const int U = compile_sectors(n, k, masks, &tab);
+  if (U < 0) return DSE_ERR_ARG;
+  if (offsets) {
+    for (int s = 0; s < k; ++s) offsets[s] = tab[s].off;
+    offsets[k] = U;
+  }
+  return U;
+}
+
+int dse_set_sectors(dse_ctx* ctx, int problem, int k, const uint64_t* masks) {
+  if (!ctx) return DSE_ERR_ARG;
+  int first = 0, count = 1;
+  int rc = init_members(ctx, problem, &first, &count, "dse_set_sectors");
+  if (rc) return rc;
+  if (k < 0 || k > DSE_MAX_SECTOR_SETS)
+    return fail(ctx, DSE_ERR_ARG, "dse_set_sectors: k must be in 0.." + std::to_string(DSE_MAX_SECTOR_SETS));
+  HIPC(hipSetDevice(ctx->device));
+  if (k == 0) {
+    (void)sync_all(ctx);
+    for (int i = 0; i < count; ++i) free_sectors(ctx->probs[first + i]);
+    return DSE_OK;
+  }
+  std::vector<SectorEntry> tab;
+  if (compile_sectors(ctx->probs[first].n, k, masks, &tab) < 0)
+    return fail(ctx, DSE_ERR_ARG, "dse_set_sectors: null masks, a bit at or above n, m & cm != 0 or cv & ~cm != 0");
+  // the new tables beside the old ones: a failed allocation leaves the previous sets in place
+  std::vector<SectorEntry*> fresh(count, nullptr);
+  hipError_t he = hipSuccess;
+  for (int i = 0; i < count && he == hipSuccess; ++i) {
+    he = hipMalloc(&fresh[i], tab.size() * sizeof(SectorEntry));
+    if (he != hipSuccess) fresh[i] = nullptr;
+    if (he == hipSuccess) he = hipMemcpy(fresh[i], tab.data(), tab.size() * sizeof(SectorEntry), hipMemcpyHostToDevice);
+  }
+  if (he != hipSuccess) {
+    (void)hipGetLastError();
+    for (SectorEntry* b : fresh)
+      if (b) (void)hipFree(b);
+    return fail(ctx, he == hipErrorOutOfMemory ? DSE_ERR_OOM : DSE_ERR_HIP, std::string("dse_set_sectors: ") + hipGetErrorString(he));
+  }
+  (void)sync_all(ctx);
+  for (int i = 0; i < count; ++i) {
+    HostProblem& P = ctx->probs[first + i];
+    free_sectors(P);
+    P.sec_tab = tab;
+    P.d_sec_tab = fresh[i];
+  }
+  return DSE_OK;
+}
+
+int dse_sectors(const dse_ctx* ctx, int problem) {
+  if (!ctx || problem < 0 || problem >= (int)ctx->probs.size()) return DSE_ERR_ARG;
+  return ctx->probs[problem].sec_k();
+}
+
+int dse_sector_units(const dse_ctx* ctx, int problem) {
+  if (!ctx || problem < 0 || problem >= (int)ctx->probs.size()) return DSE_ERR_ARG;
+  return ctx->probs[problem].sec_units();
+}
+
 int dse_set_initial_product(dse_ctx* ctx, int problem, const double* amp) {
   if (!ctx) return DSE_ERR_ARG;
   int first = 0, count = 1;
@@ -4431,6 +4525,7 @@ int dse_set_hamiltonian(dse_ctx* ctx, int problem, const double* field, const do
     f.init_amp = std::move(P.init_amp);
     f.ovl_refs = std::move(P.ovl_refs), f.d_ovl_tab = P.d_ovl_tab;
     f.str_tab = std::move(P.str_tab), f.d_str_tab = P.d_str_tab;
+    f.sec_tab = std::move(P.sec_tab), f.d_sec_tab = P.d_sec_tab;
     P = std::move(f);
   }
   return DSE_OK;

@@ -23,6 +23,9 @@ constexpr int kSmallOverlapStride = 2 * 16 + 2;
 // operator strings per problem and output: Re, Im of string k at [2 k], [2 k + 1], ||psi||^2 at [128]
 // (string_stride(64): every register's record is sized for the cap)
 constexpr int kSmallStringStride = 2 * 64 + 2;
+// sector populations per problem and output: set k's bins from [off_k], ||psi||^2 at [160]
+// (sector_stride(16 x 10): 16 sets of at most 9 counted bits; every register's record is sized for that)
+constexpr int kSmallSectorStride = 16 * 10 + 2;
 
 struct SmallProb {
   double2* state;          // [2^n] the state at the start of the next launch
@@ -41,13 +44,17 @@ struct SmallProb {
   // the register's compiled operator strings (null, 0: none)
   const StringEntry* str_tab;
   int str_k;
+  // the register's sector sets (null, 0: none)
+  const SectorEntry* sec_tab;
+  int sec_k;
 };
 
 // One launch: intervals m0 .. m0 + n_int - 1 of problems sel[0 .. count) (all with n qubits);
 // out[problem][m + 1][8] = raw observable sums of psi(t_{m+1}) (dse_runtime.hip finish_obs).
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
                         const int* iv_set, double* out, hipStream_t st, double* sites = nullptr,
-                        double* pairs = nullptr, double* ovl = nullptr, double* strs = nullptr);
+                        double* pairs = nullptr, double* ovl = nullptr, double* strs = nullptr,
+                        double* secs = nullptr);
 // out[problem][0][8] = observable sums of the state buffer (psi0)
 // sites non-null (both launches): also sites[problem][m][kSmallSiteStride], the site-resolved sums
 // pairs non-null (both launches): also pairs[problem][m][kSmallPairStride], the two-spin sums
@@ -56,8 +63,11 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 // strs non-null (both launches): also strs[problem][m][kSmallStringStride], the operator strings of
 // the problem's table (a problem without strings: its records are left unwritten); the kernels are
 // then k_small_str / k_small_obs0_str, which take ovl and strs as run-time-optional pointers
+// secs non-null (both launches): also secs[problem][m][kSmallSectorStride], the sector populations of
+// the problem's sets (a problem without sets: its records are left unwritten); the kernels are then
+// k_small_sec / k_small_obs0_sec, which take ovl, strs and secs as run-time-optional pointers
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
                              hipStream_t st, double* sites = nullptr, double* pairs = nullptr,
-                             double* ovl = nullptr, double* strs = nullptr);
+                             double* ovl = nullptr, double* strs = nullptr, double* secs = nullptr);
 
 }  // namespace dse

@@ -198,6 +198,45 @@ __device__ __forceinline__ void small_string_sums(const double2* w, int lane, bo
   }
 }
 
+// Sector populations of the state in LDS w (the record of dse_sectors.hip at the stride
+// kSmallSectorStride): sets in table order, the selection applied per amplitude, then
+// sector_wave_bins over the row bits (register bits 6 ..) and the lane bits; lane 0 holds the set's
+// bins under compile-time indices and stores them.  K = 0: nothing is written.
+template <int N>
+__device__ __forceinline__ void small_sector_sums(const double2* w, int lane, bool live,
+                                                  const SectorEntry* __restrict__ tab, int K, double* o) {
+  constexpr int R = SmallGeo<N>::R, LR = N >= 6 ? N - 6 : 0, VL = LR + 7;
+  if (K <= 0) return;
+  double p2[R];
+  double n2 = 0.0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const double2 p = live ? w[r * 64 + lane] : make_double2(0.0, 0.0);
+    p2[r] = p.x * p.x + p.y * p.y;
+    n2 += p2[r];
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
+  const int U = tab[K - 1].off + tab[K - 1].bins;
+  for (int i = U + lane; i < kSmallSectorStride; i += 64) o[i] = (i == kSmallSectorStride - 2) ? n2 : 0.0;
+#pragma unroll 1
+  for (int k = 0; k < K; ++k) {
+    const uint32_t m = (uint32_t)tab[k].m, cm = (uint32_t)tab[k].cm, cv = (uint32_t)tab[k].cv;
+    double q[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) q[r] = (((uint32_t)(r * 64 + lane)) & cm) == cv ? p2[r] : 0.0;
+    double v[VL];
+    sector_wave_bins<LR>(q, m >> 6, m & 63u, v);
+    if (lane == 0) {
+      const int bins = tab[k].bins;
+      double* ok = o + tab[k].off;
+#pragma unroll
+      for (int c = 0; c < VL; ++c)
+        if (c < bins) ok[c] = v[c];
+    }
+  }
+}
+
 #define DSE_SMALL_OVL 0
 #include "dse_small_kernels.inc"
 #undef DSE_SMALL_OVL
@@ -207,16 +246,22 @@ __device__ __forceinline__ void small_string_sums(const double2* w, int lane, bo
 #define DSE_SMALL_OVL 2
 #include "dse_small_kernels.inc"
 #undef DSE_SMALL_OVL
+#define DSE_SMALL_OVL 3
+#include "dse_small_kernels.inc"
+#undef DSE_SMALL_OVL
 
 }  // namespace
 
 #define DSE_SMALL_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
 
 // (SITES, PAIRS) of a launch from the two output pointers; with ovl the _ovl kernel of the same two,
-// with strs the _str kernel (ovl then optional at run time)
+// with strs the _str kernel (ovl then optional at run time), with secs the _sec kernel (ovl and strs
+// then optional at run time)
 #define DSE_SMALL_LAUNCH(K, q, S_, P_, ...)                                                                  \
   do {                                                                                                       \
-    if (strs)                                                                                                \
+    if (secs)                                                                                                \
+      hipLaunchKernelGGL((K##_sec<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl, strs, secs); \
+    else if (strs)                                                                                                \
       hipLaunchKernelGGL((K##_str<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl, strs); \
     else if (ovl)                                                                                               \
       hipLaunchKernelGGL((K##_ovl<q, S_, P_>), dim3(count), dim3(64), 0, st, __VA_ARGS__, sites, pairs, ovl); \
@@ -237,7 +282,7 @@ __device__ __forceinline__ void small_string_sums(const double2* w, int lane, bo
 
 hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count, int m0, int n_int,
                         const int* iv_set, double* out, hipStream_t st, double* sites, double* pairs,
-                        double* ovl, double* strs) {
+                        double* ovl, double* strs, double* secs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \
@@ -251,7 +296,8 @@ hipError_t launch_small(int n, const SmallProb* probs, const int* sel, int count
 }
 
 hipError_t launch_small_obs0(int n, const SmallProb* probs, const int* sel, int count, double* out,
-                             hipStream_t st, double* sites, double* pairs, double* ovl, double* strs) {
+                             hipStream_t st, double* sites, double* pairs, double* ovl, double* strs,
+                             double* secs) {
   if (count <= 0) return hipSuccess;
   switch (n) {
 #define X(q) \

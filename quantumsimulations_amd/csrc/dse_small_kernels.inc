@@ -2,10 +2,15 @@
 // once per form: DSE_SMALL_OVL 0, k_small / k_small_obs0 (the text below is then exactly what it was
 // before the overlaps existed, so those instances keep their code), DSE_SMALL_OVL 1, k_small_ovl /
 // k_small_obs0_ovl with one more output pointer, and DSE_SMALL_OVL 2, k_small_str / k_small_obs0_str
-// with two more, the overlaps' and the operator strings', each optional at run time (null: skipped).
+// with two more, the overlaps' and the operator strings', each optional at run time (null: skipped),
+// and DSE_SMALL_OVL 3, k_small_sec / k_small_obs0_sec with a third, the sector populations', optional
+// in the same way.
 // A device function holding the body, called from two kernels, is not equivalent: inlined, the
 // existing instances came out with other register counts.
-#if DSE_SMALL_OVL == 2
+#if DSE_SMALL_OVL == 3
+#define DSE_SMALL_NAME(k) k##_sec
+#define DSE_SMALL_OVL_PARAM , double* __restrict__ ovl, double* __restrict__ strs, double* __restrict__ secs
+#elif DSE_SMALL_OVL == 2
 #define DSE_SMALL_NAME(k) k##_str
 #define DSE_SMALL_OVL_PARAM , double* __restrict__ ovl, double* __restrict__ strs
 #elif DSE_SMALL_OVL
@@ -197,13 +202,18 @@ DSE_SMALL_NAME(k_small)(const SmallProb* __restrict__ probs, const int* __restri
       small_site_sums<N>(w, lane, live, sites + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallSiteStride);
     if (PAIRS)
       small_pair_sums<N>(w, lane, live, pairs + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallPairStride);
-#if DSE_SMALL_OVL == 2
+#if DSE_SMALL_OVL >= 2
     if (ovl)
       small_overlap_sums<N>(w, lane, live, P.ovl_refs, P.ovl_k,
                             ovl + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallOverlapStride);
     if (strs)
       small_string_sums<N>(w, lane, live, P.str_tab, P.str_k,
                            strs + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallStringStride);
+#if DSE_SMALL_OVL == 3
+    if (secs)
+      small_sector_sums<N>(w, lane, live, P.sec_tab, P.sec_k,
+                           secs + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallSectorStride);
+#endif
 #elif DSE_SMALL_OVL
     small_overlap_sums<N>(w, lane, live, P.ovl_refs, P.ovl_k,
                           ovl + ((size_t)sel[blockIdx.x] * P.n_t + (m + 1)) * kSmallOverlapStride);
@@ -264,11 +274,15 @@ DSE_SMALL_NAME(k_small_obs0)(const SmallProb* __restrict__ probs, const int* __r
   }
   if (SITES) small_site_sums<N>(w, lane, live, sites + (size_t)sel[blockIdx.x] * P.n_t * kSmallSiteStride);
   if (PAIRS) small_pair_sums<N>(w, lane, live, pairs + (size_t)sel[blockIdx.x] * P.n_t * kSmallPairStride);
-#if DSE_SMALL_OVL == 2
+#if DSE_SMALL_OVL >= 2
   if (ovl)
     small_overlap_sums<N>(w, lane, live, P.ovl_refs, P.ovl_k, ovl + (size_t)sel[blockIdx.x] * P.n_t * kSmallOverlapStride);
   if (strs)
     small_string_sums<N>(w, lane, live, P.str_tab, P.str_k, strs + (size_t)sel[blockIdx.x] * P.n_t * kSmallStringStride);
+#if DSE_SMALL_OVL == 3
+  if (secs)
+    small_sector_sums<N>(w, lane, live, P.sec_tab, P.sec_k, secs + (size_t)sel[blockIdx.x] * P.n_t * kSmallSectorStride);
+#endif
 #elif DSE_SMALL_OVL
   small_overlap_sums<N>(w, lane, live, P.ovl_refs, P.ovl_k, ovl + (size_t)sel[blockIdx.x] * P.n_t * kSmallOverlapStride);
 #endif

@@ -42,6 +42,7 @@ __all__ = [
     "build_hamiltonian_rare", "initial_state_rare", "dims_with_rare",
     "simulate_rare_from", "simulate_rare_sequence", "simulate_rare_overlaps", "rotation_matrices",
     "simulate_rare_strings", "op_strings_by_bit", "rdm_strings", "rdm_from_string_values",
+    "simulate_rare_sectors", "sector_masks_by_bit", "mqc_intensities", "sector_moments",
 ]
 
 _ENGINES: Dict[int, object] = {}
@@ -328,13 +329,16 @@ def _check_start(psi0, spins) -> None:
         raise ValueError("pass exactly one of psi0 and spins")
 
 
-def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng=None, ops_eng=None):
+def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng=None, ops_eng=None,
+                 secs_eng=None):
     """One evolve of the unreduced register of ``params`` from an engine-order ket or a product
     state; returns (t, obs dict, final state in engine order, the Problem).  ``refs_eng``: reference
     states of the register in engine order, (K, 2^n), or "initial" (the state the evolve starts
     from, as the engine holds it); the overlap traces (K, n_t) are then returned as a fifth item.
     ``ops_eng``: operator strings of the register by bit, (K, n) codes; their traces (K, n_t) are then
-    returned as the last item.  The engine is left cleared, so without references and strings."""
+    returned as the next item.  ``secs_eng``: sector sets of the register by bit, (K, 3) masks; their
+    traces, a list of (B_k, n_t) arrays, are then returned as the last item.  The engine is left
+    cleared, so without references, strings and sets."""
     t = time_grid(params)
     prob = build_problem(params, order="engine", reduce=False)
     eng.clear()
@@ -348,16 +352,21 @@ def _evolve_from(eng, params: DipolarRareParams, psi_eng, amps_by_site, refs_eng
             eng.set_overlap_refs(pid, eng.initial_state(pid)[None, :] if isinstance(refs_eng, str) else refs_eng)
         if ops_eng is not None:
             eng.set_op_strings(pid, ops_eng)
+        if secs_eng is not None:
+            eng.set_sectors(pid, secs_eng)
         obs, _ = eng.evolve(t, tol=_tol())
         final = eng.state(pid)
         ovl = eng.overlap_traces(pid) if refs_eng is not None else None
         strs = eng.op_string_traces(pid) if ops_eng is not None else None
+        secs = eng.sector_traces(pid) if secs_eng is not None else None
     finally:
         eng.clear()
     out = (t, {name: obs[0, j].copy() for j, name in enumerate(OBS_NAMES)}, final, prob)
     if refs_eng is not None:
         out = out + (ovl,)
-    return out if ops_eng is None else out + (strs,)
+    if ops_eng is not None:
+        out = out + (strs,)
+    return out if secs_eng is None else out + (secs,)
 
 
 def simulate_rare_from(params: DipolarRareParams, psi0=None, spins=None, return_state: bool = False,
@@ -514,6 +523,108 @@ def rdm_from_string_values(values) -> np.ndarray:
         weight = sum(1 for d in digits if d)
         rho += (v[c - 1].real * (2.0 ** weight / dim))[:, None, None] * mat[None]
     return rho
+
+
+# The alphabet of a sector set, one letter per site: w counted, . ignored, a / b selected up / down
+SECTOR_ALPHABET = "w.ab"
+MAX_SECTOR_SETS = 16  # DSE_MAX_SECTOR_SETS
+
+
+def sector_masks_by_bit(sets, site_of_bit: np.ndarray) -> np.ndarray:
+    """Sector sets over the alphabet ``"w.ab"``, one letter per site in the reference's site order
+    (each of length n_sites = len(site_of_bit)): ``w`` a counted spin, ``.`` an ignored one, ``a`` /
+    ``b`` a spin selected up / down.  Returns the ``(K, 3)`` uint64 masks by register bit (m, cm, cv)
+    that Engine.set_sectors takes: bit b of a mask is set by the letter of site ``site_of_bit[b]``.
+    1..16 sets."""
+    site_of_bit = np.asarray(site_of_bit, dtype=np.int64)
+    n = site_of_bit.size
+    if isinstance(sets, str):
+        sets = [sets]
+    sets = list(sets)
+    if sorted(site_of_bit.tolist()) != list(range(n)):
+        raise ValueError("site_of_bit must be a permutation of the sites")
+    if not 1 <= len(sets) <= MAX_SECTOR_SETS:
+        raise ValueError(f"pass 1..{MAX_SECTOR_SETS} sets")
+    out = np.zeros((len(sets), 3), dtype=np.uint64)
+    for k, w in enumerate(sets):
+        if not isinstance(w, str) or len(w) != n:
+            raise ValueError(f"set {k} must be a str of {n} letters, one per site")
+        if any(ch not in SECTOR_ALPHABET for ch in w):
+            raise ValueError(f"set {k} holds a letter outside {SECTOR_ALPHABET!r}")
+        m = cm = cv = 0
+        for b in range(n):
+            ch = w[site_of_bit[b]]
+            m |= (ch == "w") << b
+            cm |= (ch in "ab") << b
+            cv |= (ch == "b") << b
+        out[k] = (m, cm, cv)
+    return out
+
+
+def simulate_rare_sectors(params: DipolarRareParams, sets, psi0=None, spins=None, device: int | None = None):
+    """simulate_rare_from that also returns magnetisation-sector populations: ``(t, obs,
+    populations)``, ``populations[k]`` the ``(B_k, n_t)`` array of set ``sets[k]``, a str of n_sea + 1
+    letters over ``"w.ab"`` in the reference's site order (counted, ignored, selected up, selected
+    down); row j is the weight of the states with j counted spins down among those that meet the
+    selection, over <psi|psi>; 1..16 sets.  ``psi0`` / ``spins`` as in simulate_rare_from (at most
+    one); with neither the evolution starts from ``initial_state_rare(params)``.  The unreduced
+    register is used and the cached engine is left without sets.  See mqc_intensities and
+    sector_moments."""
+    if psi0 is not None and spins is not None:
+        raise ValueError("pass at most one of psi0 and spins")
+    n_sites = params.n_sea + 1
+    if isinstance(sets, str):
+        sets = [sets]
+    sets = list(sets)
+    if not 1 <= len(sets) <= MAX_SECTOR_SETS:
+        raise ValueError(f"pass 1..{MAX_SECTOR_SETS} sets")
+    prob = build_problem(params, order="engine", reduce=False)
+    if len(prob.site_of_bit) != n_sites:
+        raise ValueError("the unreduced register must hold every site")
+    masks = sector_masks_by_bit(sets, prob.site_of_bit)
+    if psi0 is None and spins is None:
+        psi0 = initial_state_rare(params)
+    amps = spin_amplitudes(spins, n_sites) if spins is not None else None
+    psi_eng = reference_to_engine_state(psi0, prob.site_of_bit) if psi0 is not None else None
+    eng = _engine(_default_device() if device is None else device)
+    out = _evolve_from(eng, params, psi_eng, amps, secs_eng=masks)
+    return out[0], out[1], out[-1]
+
+
+def mqc_intensities(P) -> np.ndarray:
+    """Multiple-quantum-coherence intensities of a pure state from its sector populations: ``P`` of
+    shape ``(n_t, B)`` (or ``(B,)``: one time), P[:, M] the population of the sector of M spins down,
+    to ``(n_t, 2 B - 1)``: column q + B - 1 holds I_q = sum_M P_M P_{M - q} for q = -(B - 1) .. B - 1,
+    the sum of |rho_xy|^2 over the pairs whose weights differ by q.  I_q = I_{-q}; for populations that
+    sum to 1 so do the intensities."""
+    p = np.asarray(P, dtype=np.float64)
+    if p.ndim == 1:
+        p = p[None, :]
+    if p.ndim != 2 or p.shape[1] < 1:
+        raise ValueError("P must have shape (n_t, B)")
+    return np.stack([np.correlate(row, row, mode="full") for row in p])
+
+
+def sector_moments(P, order: int) -> np.ndarray:
+    """``(n_t, order + 1)`` moments of the number M of spins down under the populations ``P`` of shape
+    ``(n_t, B)`` (or ``(B,)``): column 0 the total weight sum_M P_M, column 1 the mean of M, column
+    r >= 2 the central moment <(M - <M>)^r>, means taken with P / sum_M P_M.  The polarisation of the
+    counted spins is (B - 1) / 2 - <M>."""
+    p = np.asarray(P, dtype=np.float64)
+    if p.ndim == 1:
+        p = p[None, :]
+    order = int(order)
+    if p.ndim != 2 or p.shape[1] < 1 or order < 1:
+        raise ValueError("P must have shape (n_t, B) and order must be at least 1")
+    M = np.arange(p.shape[1], dtype=np.float64)
+    w = p.sum(axis=1)
+    q = p / np.where(w > 0.0, w, 1.0)[:, None]
+    mean = q @ M
+    out = np.empty((p.shape[0], order + 1))
+    out[:, 0], out[:, 1] = w, mean
+    for r in range(2, order + 1):
+        out[:, r] = np.sum(q * (M[None, :] - mean[:, None]) ** r, axis=1)
+    return out
 
 
 def rotation_matrices(vecs) -> np.ndarray:

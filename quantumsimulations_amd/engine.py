@@ -100,6 +100,7 @@ class Engine:
         self.device = device
         self.problems: list[Problem] = []
         self._dims: list[int] = []       # state size the hooks of each problem id take
+        self._sector_off: dict[int, np.ndarray] = {}  # problem id -> first unit of each sector set, then U
         if tile_bits is not None:
             self.set_option("tile_bits", tile_bits)
         self.set_option("time_kernels", 1.0 if time_kernels else 0.0)
@@ -216,6 +217,7 @@ class Engine:
         self._check(self._L.dse_clear(self._h))
         self.problems = []
         self._dims = []
+        self._sector_off = {}
 
     # -- hot path --
     def apply_h(self, pid: int, psi: np.ndarray) -> np.ndarray:
@@ -394,6 +396,63 @@ class Engine:
         """Registers whose string values the last successful evolve produced."""
         return int(self._L.dse_op_string_problems(self._h))
 
+    # -- magnetisation-sector populations (include/dse.h, feature "sector_obs") --
+    def set_sectors(self, pid: int, masks) -> None:
+        """Register ``pid`` carries the sector sets ``masks``: a ``(K, 3)`` array of register-bit masks,
+        row k = (m, cm, cv): the counted bits, the selecting bits and their values (K <=
+        DSE_MAX_SECTOR_SETS; m & cm == 0, cv within cm; a loopback partitioned register: shard 0's id
+        and masks over all n bits).  Every later evolve keeps, for every output, the populations
+        P_j = sum |psi_x|^2 / <psi|psi> over the x with (x & cm) == cv and popcount(x & m) == j,
+        j = 0 .. popcount(m).  The sets replace the previous ones; ``None`` or an empty array clears
+        them."""
+        pid = self._pid(pid)
+        if masks is None or len(masks) == 0:
+            self._check(self._L.dse_set_sectors(self._h, pid, 0, None))
+            self._sector_off.pop(pid, None)
+            return
+        x = _lib.sector_masks(masks)
+        self._check(self._L.dse_set_sectors(self._h, pid, x.shape[0], _lib.u64ptr(x)))
+        self._sector_off[pid] = _lib.sector_layout(self.problems[pid].n_qubits, x)[1]
+
+    def sectors(self, pid: int) -> int:
+        """K of register ``pid`` (0: none)."""
+        return self._check(self._L.dse_sectors(self._h, self._pid(pid)))
+
+    def sector_units(self, pid: int) -> int:
+        """U = sum_k (popcount(m_k) + 1) of register ``pid`` (0: none)."""
+        return self._check(self._L.dse_sector_units(self._h, self._pid(pid)))
+
+    def _split_sectors(self, pid: int, flat: np.ndarray):
+        off = self._sector_off[pid]
+        return [flat[off[k]:off[k + 1]].copy() for k in range(len(off) - 1)]
+
+    def sector_values(self, pid: int, psi: np.ndarray):
+        """A list of K arrays, entry k the ``(B_k,)`` populations of set k on the given state
+        (dse_sector_values: the tile kernel of the evolve).  RuntimeError for a register without
+        sets."""
+        pid = self._pid(pid)
+        dim = self._dims[pid]
+        x = np.ascontiguousarray(psi, dtype=np.complex128)
+        if x.shape != (dim,):
+            raise ValueError(f"state must have shape ({dim},)")
+        out = np.empty(max(self.sector_units(pid), 1))
+        self._check(self._L.dse_sector_values(self._h, pid, _lib.ptr(x), _lib.ptr(out)))
+        return self._split_sectors(pid, out)
+
+    def sector_traces(self, pid: int):
+        """A list of K arrays, entry k the ``(B_k, n_t)`` populations of set k at every output of the
+        last evolve, row j the sector of j counted spins down (RuntimeError before an evolve, after a
+        failed one and for a register without sets)."""
+        pid = self._pid(pid)
+        n_t = max(int(self._L.dse_sector_outputs(self._h)), 0)
+        out = np.empty((max(self.sector_units(pid), 1), max(n_t, 1)))
+        self._check(self._L.dse_get_sectors(self._h, pid, _lib.ptr(out)))
+        return self._split_sectors(pid, out)
+
+    def sector_problems(self) -> int:
+        """Registers whose sector populations the last successful evolve produced."""
+        return int(self._L.dse_sector_problems(self._h))
+
     def state(self, pid: int) -> np.ndarray:
         out = np.empty(self._dims[pid], dtype=np.complex128)
         self._check(self._L.dse_get_state(self._h, pid, _lib.ptr(out)))
@@ -465,7 +524,7 @@ class Engine:
 
     def set_hamiltonian(self, pid: int, prob: Problem) -> None:
         """Register ``pid`` gets the tables of ``prob`` (the same number of qubits); it keeps its
-        initial state, overlap references, operator strings, masks and shard layout.  The final state of the last evolve
+        initial state, overlap references, operator strings, sector sets, masks and shard layout.  The final state of the last evolve
         is dropped: call continue_from_final first (dse_set_hamiltonian)."""
         pid = self._pid(pid)
         if prob.n_qubits != self.problems[pid].n_qubits:
