@@ -48,7 +48,8 @@ extern "C" {
  * a getter (the two-spin correlators: option "pair_obs", dse_pair_obs_problems; the overlaps with
  * reference states: feature "overlap_obs", dse_overlap_problems; the operator strings: feature
  * "op_strings", dse_op_string_problems; the sector populations: feature "sector_obs",
- * dse_sector_problems). */
+ * dse_sector_problems; the leap path on uniform grids: feature "leap", options "leap" and "leap_fan",
+ * dse_leap_problems, and the host-only dse_uniform_spacing). */
 #define DSE_ABI_MINOR 1
 #define DSE_MAX_QUBITS 34
 #define DSE_N_OBS 7
@@ -241,6 +242,28 @@ const char* dse_last_error(const dse_ctx* ctx);
  *                         registers real, beside the 13-qubit ones on the 1-tile k_interval;
  *                         0 (default): the complex kernels (k_real measured at the 2-tile
  *                         k_interval's CU cost: slower on the bench's mix, 1 and 2 alike)
+ *          "leap"         the leap path (feature "leap"): on a uniform output grid, from basis states, with
+ *                         imaginary drives, the rotated state is chi = p + i q with p = cos(H' (t - t0)) e_x0
+ *                         and q = -sin(H' (t - t0)) e_x0 real, and p_{m+j} = 2 C_j p_m - p_{m-j},
+ *                         q_{m+j} = q_{m-j} - 2 S_j p_m: a launch runs ONE real Chebyshev recurrence per
+ *                         register (k_real's kernel on p_m alone, no cross-workgroup hand-off) and
+ *                         k_leap_combine forms the outputs from a ring of earlier ones.  1: whenever the
+ *                         evolve is persistent without obs_overlap, every Chebyshev register has 13 or
+ *                         14 qubits, imaginary drives and its basis state as psi(t0), outputs_per_launch
+ *                         is 2 (one output per series doubles the launches the recurrence's rounding
+ *                         grows over), alpha dt leap_fan < 400 and
+ *                         max_m |t_m - (t_0 + m dt)| <= 2 ulp(|t_last|), dt = (t_last - t_0) / (n_t - 1);
+ *                         otherwise, and with 0, the other options' choice runs unchanged, bitwise.
+ *                         -1 (default): as 1, but only where the automatic layout policy decides, i.e.
+ *                         with span_tile = -1, real = 0 and spin_limit, handoff_fences, xcd_pairs,
+ *                         coresident at their defaults.  dse_leap_problems counts its registers
+ *          "leap_fan"     the leap path: 1 one workgroup per register and launch, two outputs; 2
+ *                         (default) a second workgroup for the offsets 3 dt, 4 dt from the same p_m:
+ *                         four outputs per launch (stats outputs_per_launch = 4), a chain of
+ *                         K(4 dt) instead of 2 K(2 dt) terms per four outputs on twice the
+ *                         workgroups, and half the launches for the recurrence's rounding to grow
+ *                         over (0.4 to 0.9 % faster than 1 on the bench's 192 registers); the
+ *                         path's condition is then alpha dt < 200
  *          "spin_limit"   persistent kernels: polls of a partner workgroup's flag before a
  *                         cross-tile hand-off is declared failed (default 2^22 poll rounds, each an s_sleep 1 and
  *                         one flag load, so its wall time is set by that load's latency; the call
@@ -573,8 +596,15 @@ int dse_sector_outputs(const dse_ctx* ctx);
  * register counts once), 0 when there are none. */
 int dse_sector_problems(const dse_ctx* ctx);
 /* Host only: 1 when this library has the named feature, else 0.  Names: "site_obs", "initial_state",
- * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs". */
+ * "pair_obs", "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs", "leap". */
 int dse_has_feature(const char* name);
+/* Registers the last successful dse_evolve ran on the leap path (option "leap", feature "leap"); they
+ * are not counted in dse_stats.real_problems.  0 when there are none. */
+int dse_leap_problems(const dse_ctx* ctx);
+/* Host only: the leap path's grid rule.  1 and *delta = (t_last - t_0) / (n_t - 1) when
+ * max_m |t_m - (t_0 + m delta)| <= 2 ulp(|t_last|) and delta > 0; else 0 and *delta = 0 (one point
+ * included); DSE_ERR_ARG for a null t or n_t < 1.  delta may be null. */
+int dse_uniform_spacing(const double* t, int n_t, double* delta);
 /* Final state of one problem after dse_evolve (2^n interleaved complex). */
 int dse_get_state(dse_ctx* ctx, int problem, double* psi_out);
 /* ---- initial states other than a basis state (ABI 14.1) --------------------------------------

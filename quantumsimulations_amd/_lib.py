@@ -41,6 +41,7 @@ EXPORTED = (
     "dse_op_string_outputs", "dse_op_string_problems", "dse_op_string_masks",
     "dse_sector_layout", "dse_set_sectors", "dse_sectors", "dse_sector_units", "dse_sector_values",
     "dse_get_sectors", "dse_sector_outputs", "dse_sector_problems",
+    "dse_leap_problems", "dse_uniform_spacing",
 )
 DSE_MAX_OVERLAP_REFS = 16
 DSE_MAX_OP_STRINGS = 64
@@ -175,6 +176,8 @@ def _declare(lib):
         "dse_get_sectors": (C.c_int, [_vp, C.c_int, _dp]),
         "dse_sector_outputs": (C.c_int, [_vp]),
         "dse_sector_problems": (C.c_int, [_vp]),
+        "dse_leap_problems": (C.c_int, [_vp]),
+        "dse_uniform_spacing": (C.c_int, [_dp, C.c_int, _dp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -208,6 +211,8 @@ def lib():
                 raise ImportError("libdse.so predates the operator strings (dse_set_op_strings); rebuild it")
             if not hasattr(handle, "dse_set_sectors"):
                 raise ImportError("libdse.so predates the sector populations (dse_set_sectors); rebuild it")
+            if not hasattr(handle, "dse_leap_problems"):
+                raise ImportError("libdse.so predates the leap path (dse_leap_problems); rebuild it")
             _declare(handle)
             if handle.dse_abi_version() != DSE_ABI_VERSION or handle.dse_abi_minor() < DSE_ABI_MINOR:
                 raise ImportError("libdse.so ABI version mismatch; rebuild it")
@@ -217,8 +222,21 @@ def lib():
 
 def has_feature(name: str) -> bool:
     """Whether the loaded library has the named feature ("site_obs", "initial_state", "pair_obs",
-    "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs")."""
+    "overlap_obs", "pulse", "set_hamiltonian", "op_strings", "sector_obs", "leap")."""
     return bool(lib().dse_has_feature(name.encode()))
+
+
+def uniform_spacing(t) -> float:
+    """dse_uniform_spacing: the spacing of the output grid ``t`` when the leap path's rule calls it
+    uniform, else 0.0.  Host only."""
+    import numpy as np
+
+    tt = np.ascontiguousarray(t, dtype=np.float64)
+    d = C.c_double(0.0)
+    rc = lib().dse_uniform_spacing(ptr(tt), int(tt.size), C.byref(d))
+    if rc < 0:
+        raise ValueError("dse_uniform_spacing: at least one output time expected")
+    return float(d.value) if rc == 1 else 0.0
 
 
 def ptr(a):

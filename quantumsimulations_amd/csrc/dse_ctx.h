@@ -84,6 +84,9 @@ struct HostProblem {
   int span_s = 0;
   // real-component mode (dse_real.hip): this evolve runs the register as two real recurrences
   bool rl = false;
+  // the leap path (choose_leap; with rl): one real recurrence per launch, outputs by the time recurrence
+  bool lp = false;
+  int leap_k[kLeapMaxOut / kMaxOut] = {};  // the degree of each workgroup's pair of rows (build_coefficients)
   // custom psi(t0) (ABI 14.1; every shard of a loopback register alike): 0 the basis state psi0; 1 a
   // stored state in init_state (this shard's 2^n_local amplitudes: the one extra state-sized
   // buffer, held only while the problem has a stored state); 2 a product state, its 4 n amplitudes
@@ -333,7 +336,11 @@ struct dse_ctx {
   // real-component mode (dse_real.hip, option "real", default 0): registers of 13 or 14 qubits with
   // imaginary drives run as two real recurrences, one workgroup per component, no hand-off
   int real_mode = 0;
-  dse::rt::DevBuf<double2> d_real;           // [a | b] inputs and propagator sums of the real-mode registers
+  // the leap path (option "leap": -1 automatic (default), 0 never, 1 whenever choose_leap's conditions hold)
+  int leap = -1;
+  int leap_fan = 2;                 // option "leap_fan": workgroups per register and launch on that path (1, 2)
+  int leap_problems = 0;            // registers the last evolve ran on it (dse_leap_problems)
+  dse::rt::DevBuf<double2> d_real;          // [a | b] inputs and propagator sums of the real-mode registers
   dse::rt::DevBuf<unsigned char> d_real_tab;
   dse::rt::DevBuf<int2> d_real_items;
   int span_rb = 0;

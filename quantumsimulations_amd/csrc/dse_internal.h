@@ -166,6 +166,10 @@ struct DevProb {
   const struct RealTab* rtab;
   double* rin;
   double2* racc;
+  // the leap path (null otherwise): e^{-i beta (t_m - t0)} of every output m of the evolve, and the
+  // history ring of kLeapRing entries of 2^n (p, q)
+  const double2* lphase;
+  double2* lhist;
   // overlaps with reference states (dse_overlap.hip): the register's (shard's) ovl_k references,
   // 2^n_local amplitudes each (null, 0: none)
   const double2* const* ovl_refs;
@@ -258,7 +262,8 @@ struct alignas(16) RealTab {
 };
 // real_c (per problem, real mode): rin = [a | b] (2 x 2^n doubles), racc = [output j][component c]
 // blocks of 2^n complex propagator sums
-hipError_t launch_real(const DevProb* probs, const int2* items, int n_items, int set, int n_out,
+// leap != 0: the leap path's launch (item.y = the workgroup's pair of outputs, below)
+hipError_t launch_real(const DevProb* probs, const int2* items, int n_items, int set, int n_out, int leap,
                        hipStream_t st);
 // psi = i^{|x0| - |x|} (acc_a + i acc_b) of every output (into the state buffer / intermediate
 // outputs k_obs reads) and, from the last output, the next interval's [a | b]
@@ -269,6 +274,21 @@ hipError_t launch_real_init(const DevProb* probs, const int2* items, int n_items
 // after launch_real_init, for the listed registers with a custom psi(t0) (RealTab::x0 ==
 // kRealFromBuffer): [a | b] = [Re phi0 | Im phi0] from the state buffer buf[0] (dse_init.hip)
 hipError_t launch_real_split(const DevProb* probs, const int2* items, int n_items, hipStream_t st);
+// The leap path (uniform grids, basis-state starts; dse_real.hip at k_leap_combine): k_real runs component 0
+// alone, rin = p_m, rows without e^{-i beta tau}.  History ring DevProb::lhist: (p, q) of output m in entry
+// m % kLeapRing.  A launch at output m0 of n <= kLeapMaxOut outputs reads outputs m0 - 1 .. m0 - n and writes
+// m0 + 1 .. m0 + n while output m0 stays for the next launch: 2 n + 1 distinct entries unless m0 + j and
+// m0 - j share one (2 j a multiple of the ring), which is j = n = 4 in a ring of eight: read, then
+// written, by the same thread.
+constexpr int kLeapMaxOut = 4;  // two workgroups per register (option leap_fan = 2), kMaxOut sums each
+constexpr int kLeapRing = 8;
+constexpr int kLeapKShift = 4;  // a launch item's y: the workgroup's pair of outputs | its degree << kLeapKShift
+// p_0 = e_x0 into rin, (e_x0, 0) into history entry 0
+hipError_t launch_leap_init(const DevProb* probs, const int2* items, int n_items, hipStream_t st);
+// the launch at output m0: outputs m0 + 1 .. m0 + n_out from racc blocks 2 j and the history, psi where
+// launch_real_combine writes it, p of the last output into rin
+hipError_t launch_leap_combine(const DevProb* probs, const int2* items, int n_items, int q, int n_out, int m0,
+                               hipStream_t st);
 
 // Coefficient row of output j of offset set `set`: kcap1 + 1 entries, row[0].x = the degree d of
 // that output's series, row[1 + k] = a_k for k = 0..d (zero beyond): 16 B per term.

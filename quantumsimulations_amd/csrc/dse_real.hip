@@ -94,23 +94,31 @@ __device__ __forceinline__ void rd_pairs(uint32_t wbase, int tp, int hh, int pp0
 int g_real_ablate = 0;
 #endif
 
-template <int L, int ABL>
-__device__ __forceinline__ void real_body(RealShared& S, const DevProb& P, int comp, int set, int n_out) {
+// comp: the component of rin the workgroup propagates.  LEAP (the leap path, k_leap_combine below):
+// component 0 from the set's rows row0, row0 + 1 into the racc blocks 2 row0, 2 row0 + 2, the series ending
+// at own_k, the larger degree of the workgroup's own rows (from the host, in the item), not the register's
+template <int L, int ABL, bool LEAP>
+__device__ __forceinline__ void real_body(RealShared& S, const DevProb& P, int comp, int row0, int own_k, int set,
+                                          int n_out) {
   constexpr int NT = kRealNT, TB = kRealTB, RB = L - TB, R = 1 << RB, RP = R / 2, HRP = RP / 2;
   constexpr int RH = R / 2;  // rows per half
   constexpr int AB = R >= 32 ? 2 : 4;  // rows per propagator-sum block
   static_assert(RB >= 4 && RB <= kRealRB, "register bits");
   const int tid = threadIdx.x;
-  const int K = P.degree;
   const double s1 = P.s1;
   const size_t nn = size_t(1) << L;
   const RealTab* tab = P.rtab;
   const cptr<RealTab> ctab = cst(tab);
-  const double* crow = (const double*)coef_row(P, set, 0);
+  const double* crow = (const double*)coef_row(P, set, LEAP ? row0 : 0);
   const size_t rstride = 2 * (size_t)(P.kcap1 + 1);
   int dj[kMaxOut];
 #pragma unroll
   for (int j = 0; j < kMaxOut; ++j) dj[j] = j < n_out ? (int)crow[j * rstride] : 0;
+  const int K = LEAP ? own_k : P.degree;
+  if constexpr (LEAP) {  // the rows are uniform, their vector loads not known to be: two VGPRs the instantiation lacks
+#pragma unroll
+    for (int j = 0; j < kMaxOut; ++j) dj[j] = __builtin_amdgcn_readfirstlane(dj[j]);
+  }
 
   // ---- setup: coefficient rows, the component -> LDS, per-thread diagonal ----
   {
@@ -353,7 +361,7 @@ __device__ __forceinline__ void real_body(RealShared& S, const DevProb& P, int c
       cf[j].c[1] = nt >= 2 ? make_double2(cc[2], cc[3]) : make_double2(0.0, 0.0);
       cf[j].c[2] = nt >= 1 ? make_double2(cc[4], cc[5]) : make_double2(0.0, 0.0);
       um |= cf[j].upd ? 1 << j : 0;
-      accp[j] = P.racc + ((size_t)(2 * j + comp) << L);
+      accp[j] = P.racc + ((size_t)(LEAP ? 2 * (row0 + j) : 2 * j + comp) << L);
     }
     // NO outputs of the launch; a term where some output updates loads and stores all NO sums
     // (an output past its degree has zero coefficients: its sums pass through unchanged)
@@ -432,9 +440,25 @@ k_real(const DevProb* __restrict__ probs, const int2* __restrict__ items, int se
   const int2 it = items[blockIdx.x];
   const DevProb& P = probs[it.x];
   if (P.n == 14)
-    real_body<14, ABL>(S, P, it.y, set, n_out);
+    real_body<14, ABL, false>(S, P, it.y, 0, 0, set, n_out);
   else
-    real_body<13, ABL>(S, P, it.y, set, n_out);
+    real_body<13, ABL, false>(S, P, it.y, 0, 0, set, n_out);
+}
+
+// the leap path's launch (k_leap_combine below): item.y = g | K << kLeapKShift, g the workgroup's pair of the
+// launch's n_out outputs (rows 2 g and 2 g + 1 of the set, from component 0, p_m) and K the pair's degree
+__global__ void __launch_bounds__(kRealNT)
+k_leap_real(const DevProb* __restrict__ probs, const int2* __restrict__ items, int set, int n_out) {
+  __shared__ RealShared S;
+  const int2 it = items[blockIdx.x];
+  const DevProb& P = probs[it.x];
+  const int row0 = 2 * (it.y & ((1 << kLeapKShift) - 1)), no = min(n_out - row0, kMaxOut);
+  const int own_k = min(max(it.y >> kLeapKShift, 1), P.degree);
+  if (no <= 0) return;
+  if (P.n == 14)
+    real_body<14, 0, true>(S, P, 0, row0, own_k, set, no);
+  else
+    real_body<13, 0, true>(S, P, 0, row0, own_k, set, no);
 }
 
 // psi_j = i^{|x0| - |x|} (acc_a + i acc_b) of output j into the buffer k_obs reads (the last output:
@@ -473,6 +497,64 @@ k_real_init(const DevProb* __restrict__ probs, const int2* __restrict__ items) {
     P.rin[x] = (x == (size_t)P.rtab->x0) ? 1.0 : 0.0;
 }
 
+// ---- the leap path (uniform output grids, basis-state starts): one real recurrence per register ----
+// chi(t) = e^{i beta (t - t0)} D psi(t) / i^|x0| = p(t) + i q(t), p = cos(alpha H~' (t - t0)) e_x0 and
+// q = -sin(alpha H~' (t - t0)) e_x0, both real.  With C_j = cos(alpha H~' j delta), S_j = sin(alpha H~' j delta):
+//     p_{m+j} = 2 C_j p_m - p_{m-j},   q_{m+j} = q_{m-j} - 2 S_j p_m      (m >= j)
+//     p_j = C_j p_0,                   q_j = -S_j p_0                     (m = 0)
+// k_real runs component 0 alone (rin = p_m) with the coefficient rows a_k = (2 - delta_k0) (-i)^k J_k(alpha j delta)
+// (no e^{-i beta tau}: real for even k, imaginary for odd k), which leaves (C_j p_m, -S_j p_m) in racc block 2 j.
+// With the fan-out (option leap_fan = 2) a second workgroup per register runs the offsets 3 delta, 4 delta from
+// the same p_m (item.y = 1: rows 2, 3 of the set, racc blocks 4, 6), so a launch covers four outputs.
+// k_leap_combine, launch at output m0, per output j < n_out <= kLeapMaxOut: the identities from the history
+// ring (output m in entry m % kLeapRing; one thread does all the outputs of an amplitude in order, and
+// an output overwrites an entry only this launch's same j or no output reads, dse_internal.h), psi =
+// i^{|x0| - |x|} e^{-i beta (t_m - t0)} (p + i q) where k_real_combine writes it, and p of the last output as
+// the next launch's input.  grid: (2^n / 256, problems of the list)
+__global__ void __launch_bounds__(256)
+k_leap_combine(const DevProb* __restrict__ probs, const int2* __restrict__ items, int q, int n_out, int m0) {
+  const DevProb& P = probs[items[blockIdx.y].x];
+  const size_t nn = size_t(1) << P.n;
+  const size_t x = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (x >= nn) return;
+  const uint32_t px = (uint32_t)__popcll((unsigned long long)x);
+  const int e = ((int)P.rtab->x0pop - (int)px) & 3;
+#pragma unroll
+  for (int j = 0; j < kLeapMaxOut; ++j) {
+    if (j >= n_out) break;
+    const int m = m0 + j + 1;  // the output's index on the grid
+    const double2 a = gld(gptr(P.racc), ((size_t)(2 * j) << P.n) + x);  // (C p_m0, -S p_m0), offset (j + 1) delta
+    double pr = a.x, pi = a.y;
+    if (m0 > 0) {
+      const double2 h = gld(gptr(P.lhist), ((size_t)((m0 - j - 1) & (kLeapRing - 1)) << P.n) + x);
+      pr = 2.0 * a.x - h.x;
+      pi = h.y + 2.0 * a.y;
+    }
+    gst(gptr(P.lhist), ((size_t)(m & (kLeapRing - 1)) << P.n) + x, make_double2(pr, pi));
+    const bool last = j == n_out - 1;
+    if (last) P.rin[x] = pr;
+    const double2 ph = P.lphase[m];  // e^{-i beta (t_m - t0)}
+    const double cr = pr * ph.x - pi * ph.y, ci = pr * ph.y + pi * ph.x;
+    double2 psi;
+    psi.x = e == 0 ? cr : e == 1 ? -ci : e == 2 ? -cr : ci;
+    psi.y = e == 0 ? ci : e == 1 ? cr : e == 2 ? -ci : -cr;
+    double2* dst = last ? P.buf[q ? 0 : 2] : P.xacc + ((size_t)j << P.n);
+    gst(gptr(dst), x, psi);
+  }
+}
+
+// p_0 = e_x0 and the history entry of output 0, (p_0, q_0) = (e_x0, 0)
+__global__ void __launch_bounds__(256)
+k_leap_init(const DevProb* __restrict__ probs, const int2* __restrict__ items) {
+  const DevProb& P = probs[items[blockIdx.y].x];
+  const size_t nn = size_t(1) << P.n;
+  for (size_t x = (size_t)blockIdx.x * 256 + threadIdx.x; x < nn; x += (size_t)gridDim.x * 256) {
+    const double v = (x == (size_t)P.rtab->x0) ? 1.0 : 0.0;
+    P.rin[x] = v;
+    P.lhist[x] = make_double2(v, 0.0);
+  }
+}
+
 }  // namespace
 
 hipError_t set_real_ablate(int mask) {
@@ -490,10 +572,14 @@ hipError_t real_occupancy(int* blocks_per_cu) {
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_real<0>, kRealNT, 0);
 }
 
-hipError_t launch_real(const DevProb* probs, const int2* items, int n_items, int set, int n_out,
+hipError_t launch_real(const DevProb* probs, const int2* items, int n_items, int set, int n_out, int leap,
                        hipStream_t st) {
   if (n_items <= 0) return hipSuccess;
   const dim3 g(n_items), b(kRealNT);
+  if (leap) {
+    hipLaunchKernelGGL(k_leap_real, g, b, 0, st, probs, items, set, n_out);
+    return hipGetLastError();
+  }
 #ifdef DSE_DIAG
   switch (g_real_ablate) {
     case 1: hipLaunchKernelGGL(k_real<1>, g, b, 0, st, probs, items, set, n_out); break;
@@ -515,6 +601,19 @@ hipError_t launch_real_combine(const DevProb* probs, const int2* items, int n_it
   if (n_items <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_real_combine, dim3((1u << 14) / 256, n_out, n_items), dim3(256), 0, st, probs, items, q,
                      n_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_leap_combine(const DevProb* probs, const int2* items, int n_items, int q, int n_out, int m0,
+                               hipStream_t st) {
+  if (n_items <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_leap_combine, dim3((1u << 14) / 256, n_items), dim3(256), 0, st, probs, items, q, n_out, m0);
+  return hipGetLastError();
+}
+
+hipError_t launch_leap_init(const DevProb* probs, const int2* items, int n_items, hipStream_t st) {
+  if (n_items <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_leap_init, dim3(32, n_items), dim3(256), 0, st, probs, items);
   return hipGetLastError();
 }
 

@@ -1214,6 +1214,10 @@ const Option kOptions[] = {
     {"span", &dse_ctx::span, OptCheck::Range, OptEffect::Store, 0, kSpanMaxTop, "span must be in 0..4"},
     // real-component mode for registers of 13 / 14 qubits (imaginary drives)
     {"real", &dse_ctx::real_mode, OptCheck::Whole, OptEffect::Store, 0, 2, "real must be 0, 1 or 2"},
+    // the leap path on uniform grids: -1 automatic, 0 never, 1 whenever its conditions hold
+    {"leap", &dse_ctx::leap, OptCheck::Whole, OptEffect::Store, -1, 1, "leap must be -1, 0 or 1"},
+    // the leap path: workgroups per register and launch, two outputs each
+    {"leap_fan", &dse_ctx::leap_fan, OptCheck::Whole, OptEffect::Store, 1, 2, "leap_fan must be 1 or 2"},
     // spanning registers: tile bits L (0 off, -1 auto); n > L qubits span 2^(n-L) tiles
     {"span_tile", &dse_ctx::span_tile, OptCheck::Range, OptEffect::Store, 10, 13, "span_tile must be -1, 0 or in 10..13", {0, -1}},
     // amplitudes per thread of k_span: 2^span_rb (0: 512 threads)
@@ -2623,7 +2627,25 @@ int dse_has_feature(const char* name) {
   if (!name) return 0;
   const std::string k(name);
   return k == "site_obs" || k == "initial_state" || k == "pair_obs" || k == "overlap_obs" || k == "pulse" ||
-         k == "set_hamiltonian" || k == "op_strings" || k == "sector_obs";
+         k == "set_hamiltonian" || k == "op_strings" || k == "sector_obs" || k == "leap";
+}
+
+int dse_leap_problems(const dse_ctx* ctx) { return ctx ? ctx->leap_problems : DSE_ERR_ARG; }
+
+// the leap path's uniform-grid rule: max_m |t_m - (t_0 + m delta)| <= 2 ulp(|t_last|) with
+// delta = (t_last - t_0) / (n_t - 1)
+int dse_uniform_spacing(const double* t, int n_t, double* delta) {
+  if (!t || n_t < 1) return DSE_ERR_ARG;
+  if (delta) *delta = 0.0;
+  if (n_t < 2) return 0;
+  const double d = (t[n_t - 1] - t[0]) / (n_t - 1);
+  const double last = std::fabs(t[n_t - 1]);
+  const double ulp = std::nextafter(last, std::numeric_limits<double>::infinity()) - last;
+  if (!(d > 0.0)) return 0;
+  for (int m = 0; m < n_t; ++m)
+    if (!(std::fabs(t[m] - (t[0] + m * d)) <= 2.0 * ulp)) return 0;
+  if (delta) *delta = d;
+  return 1;
 }
 
 // ---- spanning registers (dse_span.hip) ------------------------------------------------------
@@ -2842,6 +2864,7 @@ struct EvolvePlan {
   int matrix_pi = -1;    // the register in propagator-matrix mode (matrix_run), or -1; its time step
   double matrix_dt = 0.0;
   int M = 1;  // outputs per launch
+  double leap_dt = 0.0;  // > 0: the evolve runs on the leap path (choose_leap), the grid's spacing
   std::vector<IntervalGroup> groups;
   std::vector<std::vector<double>> set_tau;  // per coefficient set: offsets t[m0 + j + 1] - t[m0], j < n_out
   size_t chunk = 1;                          // output slots of the partial arenas per flush
@@ -3039,6 +3062,45 @@ void choose_real(dse_ctx* ctx, const EvolvePlan& pl) {
     P.rl = real_mode && n_cheb > 0 && !P.side() && (ctx->real_mode == 1 || (real_eligible(P) && P.n_tiles == 2));
 }
 
+// the spacing delta of a uniform output grid, max_m |t_m - (t_0 + m delta)| <= 2 ulp(|t_last|) with
+// delta = (t_last - t_0) / (n_t - 1); 0 when the grid is not uniform (or has one point)
+double uniform_spacing(const double* t, int n_t) {
+  double delta = 0.0;
+  return dse_uniform_spacing(t, n_t, &delta) == 1 ? delta : 0.0;
+}
+
+// The leap path (option leap; dse_real.hip at k_leap_combine): on a uniform grid, from basis states,
+// a launch needs one real recurrence per register (k_real's component 0 on p_m) and the outputs
+// follow from the time recurrence.  Taken when the evolve is persistent without obs_overlap, every
+// Chebyshev register is real_eligible (13 or 14 qubits, imaginary drives, whole) and starts from its
+// basis state, outputs_per_launch is 2, alpha delta leap_fan < 400 and the grid is uniform.  leap = -1 (default) is part of the
+// automatic layout policy: only with span_tile = -1, real = 0 and the hand-off kernels' own knobs
+// (spin_limit, handoff_fences, xcd_pairs, coresident) at their defaults, so a caller that pins
+// k_interval, k_span or k_real keeps the kernel it names.
+void choose_leap(dse_ctx* ctx, EvolvePlan& pl) {
+  pl.leap_dt = 0.0;
+  for (auto& P : ctx->probs) P.lp = false;
+  const bool automatic = ctx->span_tile == -1 && ctx->real_mode == 0 && ctx->hk.spin_limit == HandoffKnobs().spin_limit &&
+                         ctx->hk.fences == 0 && ctx->xcd_pairs == 1 && ctx->coresident == 0;
+  if (ctx->leap == 0 || (ctx->leap < 0 && !automatic) || !pl.persistent || ctx->obs_overlap) return;
+  // the time recurrence amplifies a launch's rounding by the number of launches after it: two outputs per
+  // series only (one per series doubles the launches: 5e-13 of norm after 30 outputs against 6e-14, measured)
+  if (ctx->outputs_per_launch != kMaxOut) return;
+  const double delta = uniform_spacing(pl.t, pl.n_t);
+  if (!(delta > 0.0)) return;
+  int n_cheb = 0;
+  for (auto& P : ctx->probs) {
+    if (P.side()) continue;
+    ++n_cheb;
+    if (!real_eligible(P) || P.init_kind != 0) return;
+    // (as choose_outputs_per_launch's rule for two outputs per series; the fan-out's series reach twice as far)
+    if (!(0.5 * (P.e_max - P.e_min) * delta * ctx->leap_fan < 400.0)) return;
+  }
+  if (n_cheb == 0) return;
+  pl.leap_dt = delta;
+  for (auto& P : ctx->probs) P.rl = P.lp = !P.side();
+}
+
 // streaming: registers of more than one 2^13 tile take the Walsh-Hadamard engine (option wht)
 int choose_wht(dse_ctx* ctx, EvolvePlan& pl) {
   pl.any_dist_step = pl.any_dist;
@@ -3069,6 +3131,8 @@ void choose_outputs_per_launch(dse_ctx* ctx, EvolvePlan& pl) {
     if (!P.side()) pl.all_span = pl.all_span && P.span_s > 0 && !P.rl;
   if (pl.persistent && max_z < 400.0)
     pl.M = std::max(1, std::min(pl.all_span ? ctx->span_outputs : ctx->outputs_per_launch, pl.n_t - 1));
+  // the leap path's fan-out: leap_fan workgroups per register, kMaxOut outputs each, from the same p_m
+  if (pl.leap_dt > 0.0) pl.M = std::max(1, std::min(kMaxOut * ctx->leap_fan, pl.n_t - 1));
   pl.obs_ovl = pl.persistent && ctx->obs_overlap;
 }
 
@@ -3076,10 +3140,20 @@ void choose_outputs_per_launch(dse_ctx* ctx, EvolvePlan& pl) {
 int group_intervals(dse_ctx* ctx, EvolvePlan& pl) {
   const double* t = pl.t;
   const int n_t = pl.n_t, M = pl.M;
+  if (pl.leap_dt > 0.0) {  // the leap path: one set, the offsets j delta; a tail launch takes its first rows
+    std::vector<double> tau(M);
+    for (int j = 0; j < M; ++j) tau[j] = (j + 1) * pl.leap_dt;
+    pl.set_tau.push_back(tau);
+  }
   for (int m0 = 0; m0 + 1 < n_t; m0 += M) {
     IntervalGroup g;
     g.m0 = m0;
     g.n_out = std::min(M, n_t - 1 - m0);
+    if (pl.leap_dt > 0.0) {
+      g.set = 0;
+      pl.groups.push_back(g);
+      continue;
+    }
     std::vector<double> tau(g.n_out);
     for (int j = 0; j < g.n_out; ++j) tau[j] = t[m0 + j + 1] - t[m0];
     g.set = -1;
@@ -3116,13 +3190,27 @@ int build_coefficients(dse_ctx* ctx, EvolvePlan& pl) {
     const double alpha = std::max(0.5 * (P.e_max - P.e_min), 1e-300);
     const double beta = 0.5 * (P.e_max + P.e_min);
     int deg = 1, kmax = 0;
-    coef_rc[pi] = cheb_rows(alpha, beta, pl.set_tau, M, pl.tol, ctx->max_degree, &deg, &coef_rows[pi], &kmax);
+    // (the leap path's rows carry no e^{-i beta tau}: a_k real for even k, imaginary for odd k; the
+    // combine applies the phase of each output's own time)
+    // Its series are cut at tol / launches.  A truncation error E of C_j shifts cos(theta) of every
+    // eigenmode in every launch alike; where |cos(theta)| = 1 the time recurrence then grows like
+    // cosh(N sqrt(2 E)) - 1 = N^2 E over N launches (measured on the bench's 50 launches at E = tol = 1e-14:
+    // 9e-12 of norm, against the N E = 6e-13 of the chained propagators), so E = tol / N keeps the
+    // evolve's total at the chained schemes' N tol.  J_k falls so fast that this is 4 to 6 terms of 191.
+    const double tol = P.lp ? pl.tol / (double)std::max<size_t>(1, pl.groups.size()) : pl.tol;
+    coef_rc[pi] = cheb_rows(alpha, P.lp ? 0.0 : beta, pl.set_tau, M, tol, ctx->max_degree, &deg, &coef_rows[pi], &kmax);
     if (coef_rc[pi] == DSE_ERR_CONVERGENCE)
       coef_msg[pi] = "Chebyshev degree " + std::to_string(kmax) + " exceeds max_degree; use a finer output grid";
     else if (coef_rc[pi] != DSE_OK)
       coef_msg[pi] = "bessel failed";
     if (coef_rc[pi] != DSE_OK) return;
     P.degree = deg;
+    if (P.lp)  // the leap path: the degree of each workgroup's pair of rows, which its launch items carry
+      for (int g = 0; g * kMaxOut < M; ++g) {
+        P.leap_k[g] = 1;
+        for (int j = g * kMaxOut; j < std::min(M, (g + 1) * kMaxOut); ++j)
+          P.leap_k[g] = std::max(P.leap_k[g], (int)coef_rows[pi][(size_t)j * (deg + 2)].first);
+      }
     DevProb& d = ctx->h_desc[pi];
     d.kcap1 = deg + 1;
     d.degree = deg;
@@ -3180,18 +3268,30 @@ int place_output_buffers(dse_ctx* ctx, const EvolvePlan& pl) {
   }
   // real-component registers: tables, [a | b] inputs and per-output, per-component sums
   Arena tabs;
-  std::vector<size_t> tab_off(ctx->probs.size(), 0);
+  std::vector<size_t> tab_off(ctx->probs.size(), 0), phase_off(ctx->probs.size(), 0);
   size_t need = 0;  // in double2 units
   for (size_t pi = 0; pi < ctx->probs.size(); ++pi) {
     const HostProblem& P = ctx->probs[pi];
     ctx->h_desc[pi].rtab = nullptr;
     ctx->h_desc[pi].rin = nullptr;
     ctx->h_desc[pi].racc = nullptr;
+    ctx->h_desc[pi].lphase = nullptr;
+    ctx->h_desc[pi].lhist = nullptr;
     if (!P.rl) continue;
     RealTab T;
     if ((rc = build_real_table(P, T)) != DSE_OK) return fail(ctx, rc, "real-mode tables: drives not imaginary");
     tab_off[pi] = tabs.add(&T, sizeof(T));
     need += ((size_t)1 + 2 * (size_t)M) << P.n_local;
+    if (P.lp) {  // e^{-i beta (t_m - t0)} of every output (the given t_m, not m delta), and the history ring
+      const double beta = 0.5 * (P.e_max + P.e_min);
+      std::vector<double2> ph(pl.n_t);
+      for (int m = 0; m < pl.n_t; ++m) {
+        const double a = -beta * (pl.t[m] - pl.t[0]);
+        ph[m] = make_double2(std::cos(a), std::sin(a));
+      }
+      phase_off[pi] = tabs.add(ph.data(), ph.size() * sizeof(double2));
+      need += (size_t)kLeapRing << P.n_local;
+    }
   }
   if (need == 0) return DSE_OK;
   if ((rc = upload_arena(ctx, tabs, ctx->d_real_tab, ctx->lanes[0].stream))) return rc;
@@ -3206,6 +3306,11 @@ int place_output_buffers(dse_ctx* ctx, const EvolvePlan& pl) {
     d.rin = reinterpret_cast<double*>(ctx->d_real.p + off);  // [a | b]: 2 x 2^n doubles
     d.racc = ctx->d_real.p + off + ((size_t)1 << P.n_local);
     off += ((size_t)1 + 2 * (size_t)M) << P.n_local;
+    if (P.lp) {
+      d.lphase = reinterpret_cast<const double2*>(ctx->d_real_tab.p + phase_off[pi]);
+      d.lhist = ctx->d_real.p + off;
+      off += (size_t)kLeapRing << P.n_local;
+    }
   }
   return DSE_OK;
 }
@@ -3533,7 +3638,15 @@ void order_real_items(dse_ctx* ctx, EvolvePlan& pl) {
       if (g.kind != GroupKind::Real) continue;
       const std::vector<int> pis = group_problems(pl, g);
       g.real_off = (int64_t)ritems.size();
-      for (int pi : pis) ritems.push_back(make_int2(pi, 0)), ritems.push_back(make_int2(pi, 1));
+      if (pl.leap_dt > 0.0) {
+        // the leap path: p_m alone; item (problem, g) runs the launch's outputs 2 g, 2 g + 1.  The longest
+        // series first (the last pair's), each pair's items in degree order, so a launch of n outputs
+        // takes the last ceil(n / kMaxOut) * |pis| items
+        for (int g2 = (pl.M + kMaxOut - 1) / kMaxOut - 1; g2 >= 0; --g2)
+          for (int pi : pis) ritems.push_back(make_int2(pi, g2 | (ctx->probs[pi].leap_k[g2] << kLeapKShift)));
+      } else {
+        for (int pi : pis) ritems.push_back(make_int2(pi, 0)), ritems.push_back(make_int2(pi, 1));
+      }
       g.real_count = (int64_t)ritems.size() - g.real_off;
       g.real_poff = (int64_t)ritems.size();
       for (int pi : pis) ritems.push_back(make_int2(pi, 0));
@@ -3607,7 +3720,9 @@ int write_initial_states(dse_ctx* ctx, const EvolvePlan& pl) {
   }
   for (auto& ln : ctx->lanes)  // real-component registers: [a | b] = [e_x0 | 0], or split from buf[0]
     for (auto& g : ln.groups)
-      if (g.kind == GroupKind::Real) {
+      if (g.kind == GroupKind::Real && pl.leap_dt > 0.0) {  // p_0 = e_x0 and the history's entry 0
+        HIPC(launch_leap_init(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, st0));
+      } else if (g.kind == GroupKind::Real) {
         HIPC(launch_real_init(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, st0));
         if (!custom.empty())
           HIPC(launch_real_split(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, st0));
@@ -3708,8 +3823,13 @@ int launch_persistent_group(dse_ctx* ctx, EvolvePlan& pl, Lane& ln, size_t li, L
   else if (g.kind == GroupKind::Mixed || (g.kind == GroupKind::Tiles && g.tiles != 1))
     HIPC(zero_flags(ctx->d_items + g.off, (int)g.count, ctx->d_flags.p, ln.stream));
   auto launch_g = [&](int64_t off, int cnt) -> hipError_t {
+    if (real && pl.leap_dt > 0.0) {  // only the workgroups that have outputs (order_real_items)
+      const int64_t cnt_l = (G.n_out + kMaxOut - 1) / kMaxOut * g.real_np;
+      return launch_real(ctx->d_probs, ctx->d_real_items.p + g.real_off + g.real_count - cnt_l, (int)cnt_l, set, G.n_out,
+                         1, ln.stream);
+    }
     if (real)
-      return launch_real(ctx->d_probs, ctx->d_real_items.p + g.real_off, (int)g.real_count, set, G.n_out, ln.stream);
+      return launch_real(ctx->d_probs, ctx->d_real_items.p + g.real_off, (int)g.real_count, set, G.n_out, 0, ln.stream);
     if (span)  // chunk [off, off + cnt) of the group's span launches
       return launch_span(g.span_L, g.span_rb, pl.imag_all, ctx->d_probs, ctx->d_span.p,
                          ctx->d_span_items.p + g.span_off + g.span_cuts[off],
@@ -3744,7 +3864,9 @@ int launch_persistent_group(dse_ctx* ctx, EvolvePlan& pl, Lane& ln, size_t li, L
     pl.all_flops += fl;
   }
   // real-component registers: psi of every output (computational frame) and the next [a | b]
-  if (real)
+  if (real && pl.leap_dt > 0.0)  // the leap path: the outputs by the time recurrence, and the next p_m
+    HIPC(launch_leap_combine(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, q, G.n_out, G.m0, ln.stream));
+  else if (real)
     HIPC(launch_real_combine(ctx->d_probs, ctx->d_real_items.p + g.real_poff, (int)g.real_np, q, G.n_out, ln.stream));
   return DSE_OK;
 }
@@ -3869,6 +3991,8 @@ int finish_evolve(dse_ctx* ctx, EvolvePlan& pl) {
   ctx->last_q = (int)pl.groups.size() & 1;
   for (auto& P : ctx->probs) P.final_bsel = P.side() ? 0 : (ctx->last_q ? 2 : 0);
   ctx->evolved = true;
+  ctx->leap_problems = 0;
+  for (const auto& P : ctx->probs) ctx->leap_problems += P.lp ? 1 : 0;
   for (ObsFamily f : kObsLaunchOrder) {
     ObsFamilyState& A = ctx->fam[f];
     if (!A.on) continue;
@@ -3887,7 +4011,7 @@ int fill_stats(dse_ctx* ctx, const EvolvePlan& pl, dse_stats* stats) {
     if (!P.side()) happl += (double)P.degree * (int)pl.groups.size();
     n_dense += P.dn ? 1 : 0;
     n_span += P.span_s ? 1 : 0;
-    n_real += P.rl ? 1 : 0;
+    n_real += (P.rl && !P.lp) ? 1 : 0;  // (the leap path's registers: dse_leap_problems)
     // a loopback partitioned register counts once (its shard 0)
     n_custom += (P.init_kind && (P.dist || P.shard_rank == 0)) ? 1 : 0;
     if (P.sm || P.mx) max_deg = std::max(max_deg, P.degree);
@@ -3954,6 +4078,7 @@ int evolve_impl(dse_ctx* ctx, const double* t, int n_t, double tol, double* obs_
   if ((rc = set_unit_families_on(ctx, false)) || (rc = choose_engines(ctx, pl))) return rc;
   choose_span(ctx, pl);
   choose_real(ctx, pl);
+  choose_leap(ctx, pl);
   if ((rc = choose_wht(ctx, pl))) return rc;
   choose_outputs_per_launch(ctx, pl);
   if ((rc = group_intervals(ctx, pl))) return rc;

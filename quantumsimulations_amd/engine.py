@@ -245,7 +245,10 @@ class Engine:
         st = _lib.DseStats()
         self._check(self._L.dse_evolve(self._h, _lib.ptr(tt), len(tt), float(tol), _lib.ptr(out),
                                        C.byref(st)))
-        return out, st.as_dict()
+        stats = st.as_dict()
+        # (a counter added after dse_stats was closed: a getter, include/dse.h at DSE_ABI_MINOR)
+        stats["leap_problems"] = int(self._L.dse_leap_problems(self._h))
+        return out, stats
 
     def site_observables(self, pid: int, psi: np.ndarray) -> np.ndarray:
         """(3, n): <Ix_b>, <Iy_b>, <Iz_b> of every register bit b of the normalised state ``psi``
