@@ -437,9 +437,8 @@ struct ObsFamilyDesc {
   bool amplitude;   // results are sums / ||psi|| instead of sums / ||psi||^2
   int small_stride;                                        // the small engine's stride (its widest register's)
   decltype(&launch_obs_sites) launch;                      // tile engine: S >= stride(n) doubles per tile
-  decltype(&launch_dense_obs_sites) launch_dense;          // dense engine, batched
-  decltype(&launch_dense_obs_sites_c) launch_dense_c;      // dense engine and matrix mode: one register, interleaved columns
-  double* DenseProb::*dense_out;                           // where those two write
+  decltype(&launch_dense_obs_sites) launch_dense;          // dense engine and matrix mode: the columns of a DenseCols
+  double* DenseProb::*dense_out;                           // where that one writes
   // Where the twins differ.  The site hook refuses only its own register when that is a dist shard,
   // before prepare; the pair hook refuses as the option does (obs_family_refusal), after it
   bool hook_refuses_shard_early;
@@ -451,22 +450,22 @@ struct ObsFamilyDesc {
 inline const ObsFamilyDesc kObsFamilies[kNumObsFamilies] = {
     {"site_obs", "dse_site_observables", "site", 3, [](const HostProblem& P) { return P.n; },
      [](const dse_ctx*, int n) { return site_stride(n); }, false, false,
-     kSmallSiteStride, launch_obs_sites, launch_dense_obs_sites, launch_dense_obs_sites_c, &DenseProb::sites, true, false, false},
+     kSmallSiteStride, launch_obs_sites, launch_dense_obs_sites, &DenseProb::sites, true, false, false},
     {"pair_obs", "dse_pair_observables", "pair", 5, [](const HostProblem& P) { return P.n * (P.n - 1) / 2; },
      [](const dse_ctx*, int n) { return pair_stride(n); }, false, false, kSmallPairStride, launch_obs_pairs,
-     launch_dense_obs_pairs, launch_dense_obs_pairs_c, &DenseProb::pairs, false, true, true},
+     launch_dense_obs_pairs, &DenseProb::pairs, false, true, true},
     // no option: on while the context holds references (dse_set_overlap_refs)
     {"overlap references", "dse_overlaps", "overlap", 2, [](const HostProblem& P) { return P.ovl_k(); },
      [](const dse_ctx* ctx, int) { return overlap_stride(ctx->fam[kOverlap].kmax); }, true, true, kSmallOverlapStride,
-     launch_obs_overlap, launch_dense_obs_overlap, launch_dense_obs_overlap_c, &DenseProb::ovl, false, false, true},
+     launch_obs_overlap, launch_dense_obs_overlap, &DenseProb::ovl, false, false, true},
     // no option: on while the context holds strings (dse_set_op_strings)
     {"operator strings", "dse_op_string_values", "string", 2, [](const HostProblem& P) { return P.str_k(); },
      [](const dse_ctx* ctx, int) { return string_stride(ctx->fam[kString].kmax); }, true, false, kSmallStringStride,
-     launch_obs_strings, launch_dense_obs_strings, launch_dense_obs_strings_c, &DenseProb::strs, false, false, true},
+     launch_obs_strings, launch_dense_obs_strings, &DenseProb::strs, false, false, true},
     // no option: on while the context holds sector sets (dse_set_sectors); a unit is one bin
     {"sector sets", "dse_sector_values", "sector", 1, [](const HostProblem& P) { return P.sec_units(); },
      [](const dse_ctx* ctx, int) { return sector_stride(ctx->fam[kSector].kmax); }, true, false, kSmallSectorStride,
-     launch_obs_sectors, launch_dense_obs_sectors, launch_dense_obs_sectors_c, &DenseProb::secs, false, false, true},
+     launch_obs_sectors, launch_dense_obs_sectors, &DenseProb::secs, false, false, true},
 };
 inline int family_norm_at(const ObsFamilyDesc& F, int units, size_t stride) {
   return F.per_problem_units ? (int)stride - 2 : F.comps * units;

@@ -92,59 +92,65 @@ hipError_t launch_dense_phase(const DenseProb* d, int count, int dim, const doub
 hipError_t launch_dense_project(const DenseProb* d, int count, int dim, hipStream_t st);
 hipError_t launch_dense_phase_c(const DenseProb* d, int count, int dim, const double* tau, int tb,
                                 double* P, size_t pstride, hipStream_t st);
-// observables of the tb columns of Psi' (re | im blocks as P) into d[p].obs rows t0 .. t0 + tb
-hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                            int tb, int t0, hipStream_t st);
-// observables of n_states complex states (dim amplitudes each, consecutive) of one problem
-// (d->rot = 0: the computational frame) into d->obs rows t0 .. t0 + n_states
-hipError_t launch_state_obs(const DenseProb* d, int dim, const double2* states, int n_states, int t0,
+// Where the output columns of a launch lie, for the observable kernels and k_dense_final: column j of
+// problem p has its real parts at Psi + p pstride + j colstride and its imaginary parts imoff further,
+// elements es doubles apart (dense_col).  The two layouts there are:
+struct DenseCols {
+  const double* Psi;
+  size_t pstride, colstride, imoff;
+  int es;
+  // a batched job's [re | im] blocks (as launch_dense_phase's P): tb columns of real parts, then tb of
+  // imaginary parts, problem p's block at Psi + p pstride
+  static DenseCols split(const double* Psi, size_t pstride, int dim, int tb) {
+    return {Psi, pstride, (size_t)dim, (size_t)tb * dim, 1};
+  }
+  // interleaved complex columns of ONE problem (column j = dim double2 at Psi + 2 j dim): the
+  // non-uniform FFT's blocks (dse_nufft.hip) and matrix mode's states
+  static DenseCols interleaved(const double* Psi, int dim) { return {Psi, 0, (size_t)2 * dim, 1, 2}; }
+};
+// (re, im) of column j of problem p: element x at [x * es]
+struct DenseCol {
+  const double *re, *im;
+};
+__host__ __device__ inline DenseCol dense_col(const double* Psi, size_t pstride, size_t colstride, size_t imoff,
+                                              size_t p, size_t j) {
+  const double* re = Psi + p * pstride + j * colstride;
+  return {re, re + imoff};
+}
+
+// The launchers below read tb columns `cols` of d[0 .. count) (interleaved columns: count 1) and
+// write rows t0 .. t0 + tb of each problem's record.
+// observables (d->rot = 0: the computational frame, matrix mode's states) into d[p].obs
+hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
                             hipStream_t st);
-// option site_obs: the site-resolved sums of the same columns into d[p].sites rows t0 .. t0 + tb of
-// S >= site_stride(n) doubles (X_b Y_b Z_b at [3 b + c], ||psi||^2 at [3 n]); _c: one problem,
-// interleaved complex columns (launch_dense_obs_c's and launch_state_obs's layout)
-hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                  int tb, int t0, int S, hipStream_t st);
-hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                    hipStream_t st);
-// option pair_obs (dse_pairs.hip): the two-spin sums of the same columns into d[p].pairs rows t0 ..
-// t0 + tb of S >= pair_stride(n) doubles (ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at [5 p + c],
-// ||psi||^2 at [5 NP]); _c as above
-hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                  int tb, int t0, int S, hipStream_t st);
-hipError_t launch_dense_obs_pairs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                    hipStream_t st);
-// overlaps with the registers' reference states (dse_dense.hip): the raw sums of the same columns
-// into d[p].ovl rows t0 .. t0 + tb of S = overlap_stride(K_max) doubles (Re, Im of <phi_k|psi> at
-// [2 k], [2 k + 1], ||psi||^2 at [S - 2]), the frame rotation, the psi0 phase and exp(-i shift tau_j)
-// restored as launch_dense_final does for the last column; a register without references is
-// skipped; _c as above
-hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st);
-hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st);
-// operator strings of the registers' tables (dse_strings.hip): the raw sums of the same columns into
-// d[p].strs rows t0 .. t0 + tb of S = string_stride(K_max) doubles (Re, Im of string k at [2 k],
-// [2 k + 1], ||psi||^2 at [S - 2]); a register without strings is skipped; _c as above
-hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st);
-hipError_t launch_dense_obs_strings_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st);
-// sector populations of the registers' sets (dse_sectors.hip): the raw sums of the same columns into
-// d[p].secs rows t0 .. t0 + tb of S = sector_stride(U_max) doubles (set k's bins from [off_k],
-// ||psi||^2 at [S - 2]); a register without sets is skipped; _c as above
-hipError_t launch_dense_obs_sectors(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st);
-hipError_t launch_dense_obs_sectors_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st);
-// psi(t_last) from column tb - 1 of Psi' into d[p].final_state (frame rotation, psi0 phase and
-// the shift's phase exp(-i shift tau_last) included)
-hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                              int tb, double tau_last, hipStream_t st);
-// the same two for ONE problem whose tb output columns are interleaved complex (column j = dim
-// double2 at Psi + 2 j dim: the non-uniform FFT's output, dse_nufft.hip)
-hipError_t launch_dense_obs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, hipStream_t st);
-hipError_t launch_dense_final_c(const DenseProb* d, int dim, const double* Psi, int tb, double tau_last,
-                                hipStream_t st);
+// option site_obs: the site-resolved sums into d[p].sites, S >= site_stride(n) doubles per row
+// (X_b Y_b Z_b at [3 b + c], ||psi||^2 at [3 n])
+hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                  int S, hipStream_t st);
+// option pair_obs (dse_pairs.hip): the two-spin sums into d[p].pairs, S >= pair_stride(n) doubles per
+// row (ZZ, Re ZQ, Im ZQ, Re DQ, Im DQ of pair p at [5 p + c], ||psi||^2 at [5 NP])
+hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                  int S, hipStream_t st);
+// overlaps with the registers' reference states (dse_dense.hip): the raw sums into d[p].ovl, S =
+// overlap_stride(K_max) doubles per row (Re, Im of <phi_k|psi> at [2 k], [2 k + 1], ||psi||^2 at
+// [S - 2]), the frame rotation, the psi0 phase and exp(-i shift tau_j) restored as launch_dense_final
+// does for the last column; a register without references is skipped
+hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st);
+// operator strings of the registers' tables (dse_strings.hip): the raw sums into d[p].strs, S =
+// string_stride(K_max) doubles per row (Re, Im of string k at [2 k], [2 k + 1], ||psi||^2 at
+// [S - 2]); a register without strings is skipped
+hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st);
+// sector populations of the registers' sets (dse_sectors.hip): the raw sums into d[p].secs, S =
+// sector_stride(U_max) doubles per row (set k's bins from [off_k], ||psi||^2 at [S - 2]); a register
+// without sets is skipped
+hipError_t launch_dense_obs_sectors(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st);
+// psi(t_last) from column tb - 1 into d[p].final_state (frame rotation, psi0 phase and the shift's
+// phase exp(-i shift tau_last) included)
+hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb,
+                              double tau_last, hipStream_t st);
 
 // ---- output times by a type-1 non-uniform FFT (dse_nufft.hip) ---------------------------------
 // On a uniform grid tau_j = j s + delta_j (|delta_j| lambda_max <= 1e-7) psi'(tau_j) of every output

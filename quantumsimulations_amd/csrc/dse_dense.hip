@@ -4,6 +4,7 @@
 // FP64) are library calls made by the runtime (dse_runtime.hip, dense_run); the kernels here
 // build H' from the coefficient tables, form the phase columns, and reduce the observables.
 #include "dse_dense.h"
+#include "dse_device.h"  // wave_sum
 
 namespace dse {
 namespace {
@@ -228,9 +229,7 @@ k_dense_phase_c(const DenseProb* __restrict__ probs, int dim, const double* __re
 // block sum of 7 values (256 threads = 4 waves)
 __device__ __forceinline__ void block_sum7(double* v, double (*red)[8]) {
 #pragma unroll
-  for (int k = 0; k < 7; ++k)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+  for (int k = 0; k < 7; ++k) wave_sum(v[k]);
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
 #pragma unroll
@@ -244,17 +243,14 @@ __device__ __forceinline__ void block_sum7(double* v, double (*red)[8]) {
 // Same sums as k_obs (dse_kernels.hip): 0 Ix_sea, 1 Iy_sea, 2 Iz_sea, 3 Iz_R, 4 Ix_R, 5 Iy_R,
 // 6 ||psi||^2, with <Ix_k> = sum_{bit_k(x)=0} Re(conj(psi_x) psi_{x^e_k}), <Iy_k> = Im(...).  In the
 // rotated frame psi_x = i^{-|x|} psi'_x, so conj(psi_x) psi_{x^e_k} = -i conj(psi'_x) psi'_{x^e_k}.
-// Columns j of Psi' at Psi + p pstride + j colstride (real parts), imaginary parts imoff further,
-// elements es doubles apart: the dense engine's [re | im] blocks (colstride dim, imoff tb dim,
-// es 1) or interleaved complex states (colstride 2 dim, imoff 1, es 2).
+// The columns of Psi': a DenseCols (dse_dense.h) passed as its scalars, column j through dense_col.
 __global__ void __launch_bounds__(256)
 k_dense_obs(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ Psi, size_t pstride,
             size_t colstride, size_t imoff, int es, int t0) {
   __shared__ double red[4][8];
   const DenseProb& P = probs[blockIdx.y];
   const int j = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, j);
   const int n = P.n;
   const double half_sea = 0.5 * (double)P.n_sea;
   double v[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -290,7 +286,7 @@ k_dense_obs(const DenseProb* __restrict__ probs, int dim, const double* __restri
   }
 }
 
-// Site-resolved sums of the same columns (option site_obs; layout parameters and the rotated
+// Site-resolved sums of the same columns (option site_obs; the columns' layout and the rotated
 // frame's factor -i as k_dense_obs): P.sites row t0 + j holds X_b Y_b Z_b at [3 b + c] for every bit
 // b < n and ||psi||^2 at [3 n], S doubles per row.  One pass over the column per bit (the column
 // stays in L2), its three sums reduced over the wave, then the four waves in order: no atomics.
@@ -300,8 +296,7 @@ k_dense_obs_sites(const DenseProb* __restrict__ probs, int dim, const double* __
   __shared__ double red[4][4];
   const DenseProb& P = probs[blockIdx.y];
   const int j = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, j);
   const int n = P.n;
   double* o = P.sites + (size_t)(t0 + j) * S;
   const int w = threadIdx.x >> 6;
@@ -331,9 +326,7 @@ k_dense_obs_sites(const DenseProb* __restrict__ probs, int dim, const double* __
       v[1] += zi;
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    for (int k = 0; k < 3; ++k) wave_sum(v[k]);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
       for (int k = 0; k < 3; ++k) red[w][k] = v[k];
@@ -350,15 +343,14 @@ k_dense_obs_sites(const DenseProb* __restrict__ probs, int dim, const double* __
   for (int i = 3 * n + 1 + threadIdx.x; i < S; i += 256) o[i] = 0.0;
 }
 
-// column tb - 1 of Psi' (layout as k_dense_obs: colstride, imoff, es)
+// column tb - 1 of Psi' (layout as k_dense_obs)
 __global__ void __launch_bounds__(256)
 k_dense_final(const DenseProb* __restrict__ probs, int dim, const double* __restrict__ Psi, size_t pstride,
               size_t colstride, size_t imoff, int es, int tb, double tau_last) {
   const DenseProb& P = probs[blockIdx.y];
   const uint32_t x = blockIdx.x * 256u + threadIdx.x;
   if (x >= (uint32_t)dim || !P.final_state) return;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)(tb - 1) * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, tb - 1);
   // psi_x = exp(-i shift tau) i^{|x0| - |x|} psi'_x   (rot; psi'(0) = e_x0 stands for i^{|x0|} e_x0)
   double s, c;
   if (P.refine)
@@ -374,8 +366,8 @@ k_dense_final(const DenseProb* __restrict__ probs, int dim, const double* __rest
   P.final_state[x] = make_double2(ph.x * ar - ph.y * ai, ph.x * ai + ph.y * ar);
 }
 
-// Overlaps of the same columns with the register's reference states (layout parameters as
-// k_dense_obs_sites, one workgroup per column): P.ovl row t0 + j holds Re, Im of <phi_k|psi(tau_j)>
+// Overlaps of the same columns with the register's reference states (layout as k_dense_obs, one
+// workgroup per column): P.ovl row t0 + j holds Re, Im of <phi_k|psi(tau_j)>
 // at [2 k], [2 k + 1], ||psi||^2 at [S - 2], zero elsewhere.  The references are in the reference
 // frame and the overlap sees the global phase, so the column gets back what the engine's frame
 // leaves out, exactly as k_dense_final restores it for the last column:
@@ -391,8 +383,7 @@ k_dense_obs_overlap(const DenseProb* __restrict__ probs, int dim, const double* 
   const int K = P.ovl_k;
   if (K <= 0 || !P.ovl) return;
   const int j = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, j);
   double* o = P.ovl + (size_t)(t0 + j) * S;
   const int w = threadIdx.x >> 6;
   double2 ph = make_double2(1.0, 0.0);
@@ -425,9 +416,7 @@ k_dense_obs_overlap(const DenseProb* __restrict__ probs, int dim, const double* 
       v[1] += f.x * ai - f.y * ar;
     }
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    for (int c = 0; c < 2; ++c) wave_sum(v[c]);
     if ((threadIdx.x & 63) == 0) red[w][0] = v[0], red[w][1] = v[1];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -473,66 +462,31 @@ hipError_t launch_dense_phase_c(const DenseProb* d, int count, int dim, const do
   return hipGetLastError();
 }
 
-hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                            int tb, int t0, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0);
-  return hipGetLastError();
-}
-
-hipError_t launch_state_obs(const DenseProb* d, int dim, const double2* states, int n_states, int t0,
+hipError_t launch_dense_obs(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
                             hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs, dim3(n_states, 1), dim3(256), 0, st, d, dim, (const double*)states,
-                     (size_t)0, (size_t)2 * dim, (size_t)1, 2, t0);
+  hipLaunchKernelGGL(k_dense_obs, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride, cols.colstride,
+                     cols.imoff, cols.es, t0);
   return hipGetLastError();
 }
 
-hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                              int tb, double tau_last, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_final, dim3((dim + 255) / 256, count), dim3(256), 0, st, d, dim, Psi,
-                     pstride, (size_t)dim, (size_t)tb * dim, 1, tb, tau_last);
+hipError_t launch_dense_final(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb,
+                              double tau_last, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_final, dim3((dim + 255) / 256, count), dim3(256), 0, st, d, dim, cols.Psi,
+                     cols.pstride, cols.colstride, cols.imoff, cols.es, tb, tau_last);
   return hipGetLastError();
 }
 
-hipError_t launch_dense_obs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0);
+hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                  int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride,
+                     cols.colstride, cols.imoff, cols.es, t0, S);
   return hipGetLastError();
 }
 
-hipError_t launch_dense_obs_sites(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                  int tb, int t0, int S, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0, S);
-  return hipGetLastError();
-}
-
-// interleaved complex columns, one problem: the non-uniform FFT's blocks and matrix mode's states
-hipError_t launch_dense_obs_sites_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                    hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_sites, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0, S);
-  return hipGetLastError();
-}
-
-hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_overlap, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0, S);
-  return hipGetLastError();
-}
-
-hipError_t launch_dense_obs_overlap_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_overlap, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0, S);
-  return hipGetLastError();
-}
-
-hipError_t launch_dense_final_c(const DenseProb* d, int dim, const double* Psi, int tb, double tau_last,
-                                hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_final, dim3((dim + 255) / 256, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0,
-                     (size_t)2 * dim, (size_t)1, 2, tb, tau_last);
+hipError_t launch_dense_obs_overlap(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_overlap, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride,
+                     cols.colstride, cols.imoff, cols.es, t0, S);
   return hipGetLastError();
 }
 

@@ -1,6 +1,10 @@
 // dse_device.h -- device helpers shared by the step kernels (dse_kernels.hip) and the
-// persistent interval kernel (dse_interval.hip).  Internal to libdse.
+// persistent interval kernel (dse_interval.hip); the observable kernels' tile view (ObsTile,
+// obs_partner_tile) and the wave sum every reduction uses (wave_sum: also dse_dense.hip, dse_init.hip);
+// and, the one host-side piece, the dispatch over the tile size (for_tile_bits).  Internal to libdse.
 #pragma once
+
+#include <type_traits>
 
 #include "dse_internal.h"
 
@@ -16,6 +20,76 @@ struct Geo {
   static constexpr int R = (T >= NT) ? T / NT : 1;
   static constexpr int TB = (L < LGNT) ? L : LGNT;  // tile bits carried by the thread index
 };
+
+// Host-side dispatch over the tile size: f(std::integral_constant<int, L>{}) for the run-time L of
+// [kMinTile, kMaxTile], hipErrorInvalidValue beyond.  The one list of tile sizes the step and the
+// observable kernels are instantiated for.
+#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
+template <typename F>
+hipError_t for_tile_bits(int L, F&& f) {
+  switch (L) {
+#define X(l) \
+  case l: return f(std::integral_constant<int, l>{});
+    DSE_TILE_CASES(X)
+#undef X
+    default: return hipErrorInvalidValue;
+  }
+}
+#undef DSE_TILE_CASES
+
+// The tile one workgroup of an observable kernel sums.  blockIdx.x is the launch item (problem, local
+// tile), blockIdx.y output j of the group: the last one in state buffer role bsel_last (< 3), the
+// others in intermediate output j (bsel = 3 + j) of a multi-output launch, parity xq.  Intermediate
+// outputs are unsharded and live only in this context (obs_partner_tile).  partial: this tile's record
+// of this output, S doubles per tile and out_stride per output.
+template <int L>
+struct ObsTile {
+  const DevProb& P;
+  uint32_t h, hg;       // local tile; global tile index (partitioned registers)
+  int tid, wv;          // thread, its wave
+  bool lane0, live;     // first lane of the wave; the thread holds amplitudes (tiles below one wave)
+  int bsel;
+  double* partial;
+  const double2* psi;   // the output's state, local tiles
+  size_t base;          // this tile's first amplitude in psi
+  uint32_t tmask;       // local tile index of a global one: its bits below the shard bits
+};
+template <int L>
+__device__ __forceinline__ ObsTile<L> obs_tile(const DevProb* __restrict__ probs, const int2* __restrict__ items,
+                                               int bsel_last, double* __restrict__ partial, size_t out_stride, int xq,
+                                               int S) {
+  const int2 it = items[blockIdx.x];
+  const DevProb& P = probs[it.x];
+  const uint32_t h = (uint32_t)it.y;
+  const int tid = threadIdx.x;
+  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
+  return {P,
+          h,
+          P.h_base | h,
+          tid,
+          tid >> 6,
+          (tid & 63) == 0,
+          (Geo<L>::T >= Geo<L>::NT) || (tid < Geo<L>::T),
+          bsel,
+          partial + (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S,
+          bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl)),
+          (size_t)h << L,
+          (1u << P.tbl) - 1u};
+}
+// Tile hp (global index) of the state the view reads: through tile_ptr (a partner shard's buffer
+// when hp lies there), or the local tile of the intermediate output
+template <int L>
+__device__ __forceinline__ const double2* obs_partner_tile(const ObsTile<L>& V, uint32_t hp) {
+  return V.bsel < 3 ? tile_ptr(V.P, V.bsel, hp) : V.psi + ((size_t)(hp & V.tmask) << L);
+}
+
+// Sums over the 64 lanes of a wave, in place (xor butterfly: every lane ends with the same bits).
+// Several values: their shuffles interleaved step by step.
+template <typename... D>
+__device__ __forceinline__ void wave_sum(D&... v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) ((v += __shfl_xor(v, off, 64)), ...);
+}
 
 __device__ __forceinline__ double2 cmad(double2 acc, double cr, double ci, double2 s) {
   acc.x = fma(cr, s.x, fma(-ci, s.y, acc.x));

@@ -12,8 +12,8 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "dse_internal.h"
 #include "dse_dense.h"
+#include "dse_device.h"  // wave_sum
 
 namespace dse {
 
@@ -108,11 +108,7 @@ k_dense_project(const DenseProb* __restrict__ probs, int dim) {
     sr = fma(v, phi.x, sr);
     si = fma(v, phi.y, si);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sr += __shfl_xor(sr, o, 64);
-    si += __shfl_xor(si, o, 64);
-  }
+  wave_sum(sr, si);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = sr, red[threadIdx.x >> 6][1] = si;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -361,7 +361,9 @@ hipError_t launch_basis_init(const BasisInit* list, int n_entries, uint64_t max_
 hipError_t launch_product_state(double2* out, const double* amp, int n, int n_local, uint64_t shard,
                                 hipStream_t st);
 // observables of n_out outputs of a group (grid.y): output j < n_out - 1 from intermediate
-// accumulator j, the last from state buffer role bsel; output j's partials at partial + j * out_stride
+// accumulator j, the last from state buffer role bsel; output j's partials at partial + j * out_stride.
+// This launcher and the five below share their arguments and the kernels' addressing (ObsTile,
+// dse_device.h) and dispatch over L through for_tile_bits; each checks its own bounds on S.
 hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                       double* partial, hipStream_t st, int n_out = 1, size_t out_stride = 0,
                       int xq = 0);  // xq: launch parity of the intermediate outputs (xacc_q set)

@@ -178,33 +178,24 @@ k_obs(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bse
   __shared__ double2 s_w[T];
   __shared__ double s_red[NT / 64][8];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
-  const uint32_t h = (uint32_t)it.y;
-  const uint32_t hg = P.h_base | h;
-  const int tid = threadIdx.x;
-  const bool live = (T >= NT) || (tid < T);
-  // blockIdx.y = output j of the group: the last one in state buffer role bsel_last (< 3), the
-  // others in intermediate output j (bsel = 3 + j) of a multi-output launch
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, 8);
+  const DevProb& P = V.P;
+  const int tid = V.tid;
 
   double2 own[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     own[r] = make_double2(0.0, 0.0);
-    if (live) {
-      own[r] = psi[base + r * NT + tid];
+    if (V.live) {
+      own[r] = V.psi[V.base + r * NT + tid];
       s_w[r * NT + tid] = own[r];
     }
   }
   __syncthreads();
 
   double acc[7] = {0, 0, 0, 0, 0, 0, 0};
-  if (live) {
-    const uint64_t hi = (uint64_t)hg << L;
+  if (V.live) {
+    const uint64_t hi = (uint64_t)V.hg << L;
     const double half_sea = 0.5 * (double)P.n_sea;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -256,11 +247,8 @@ k_obs(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bse
       if (!sea && !rr) continue;
       double ore = 0.0, oim = 0.0;
       {
-        if ((hg >> (b - L)) & 1u) continue;
-        const uint32_t hp = hg ^ (1u << (b - L));
-        // intermediate outputs (bsel >= 3) live only in this context, unsharded
-        const double2* src = bsel < 3 ? tile_ptr(P, bsel, hp)
-                                      : psi + ((size_t)(hp & ((1u << P.tbl) - 1u)) << L);
+        if ((V.hg >> (b - L)) & 1u) continue;
+        const double2* src = obs_partner_tile(V, V.hg ^ (1u << (b - L)));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const double2 s = src[r * NT + tid];
@@ -280,19 +268,14 @@ k_obs(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bse
   }
   // deterministic block reduction: wave butterfly, then waves in order
 #pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double v = acc[j];
+  for (int j = 0; j < 7; ++j) wave_sum(acc[j]);
+  if (V.lane0) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    acc[j] = v;
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int j = 0; j < 7; ++j) s_red[tid >> 6][j] = acc[j];
+    for (int j = 0; j < 7; ++j) s_red[V.wv][j] = acc[j];
   }
   __syncthreads();
   if (tid == 0) {
-    double* o = partial + (size_t)blockIdx.x * 8;
+    double* o = V.partial;
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
       double v = 0.0;
@@ -323,18 +306,9 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
   __shared__ double s_red[kMaxQubits][NW][3];
   __shared__ double s_n2[NW];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
-  const uint32_t h = (uint32_t)it.y;
-  const uint32_t hg = P.h_base | h;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const bool lane0 = (tid & 63) == 0;
-  const bool live = (T >= NT) || (tid < T);
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, S);
+  const DevProb& P = V.P;
+  const int tid = V.tid;
   const int n = P.n;
 
   double2 own[R];
@@ -343,8 +317,8 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     own[r] = make_double2(0.0, 0.0);
-    if (live) {
-      own[r] = psi[base + r * NT + tid];
+    if (V.live) {
+      own[r] = V.psi[V.base + r * NT + tid];
       s_w[r * NT + tid] = own[r];
     }
     p2[r] = own[r].x * own[r].x + own[r].y * own[r].y;
@@ -354,23 +328,17 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
 
   // wave butterfly of one bit's three sums (every lane takes part), lane 0 stores them
   auto wave_put = [&](int b, double x, double y, double z) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      x += __shfl_xor(x, off, 64);
-      y += __shfl_xor(y, off, 64);
-      z += __shfl_xor(z, off, 64);
-    }
-    if (lane0) {
-      s_red[b][wv][0] = x;
-      s_red[b][wv][1] = y;
-      s_red[b][wv][2] = z;
+    wave_sum(x, y, z);
+    if (V.lane0) {
+      s_red[b][V.wv][0] = x;
+      s_red[b][V.wv][1] = y;
+      s_red[b][V.wv][2] = z;
     }
   };
   {
     double v = p2sum;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane0) s_n2[wv] = v;
+    wave_sum(v);
+    if (V.lane0) s_n2[V.wv] = v;
   }
 #pragma unroll
   for (int b = 0; b < L; ++b) {
@@ -392,7 +360,7 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
       oz = -0.5 * p2sum;
     } else {
       oz = 0.5 * p2sum;
-      if (live) {
+      if (V.live) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const double2 s = s_w[(uint32_t)(r * NT + tid) ^ (1u << b)];
@@ -404,13 +372,10 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
     wave_put(b, ore, oim, oz);
   }
   for (int b = L; b < n; ++b) {
-    if ((hg >> (b - L)) & 1u) continue;  // uniform: this tile holds bit value 1, no X / Y terms
-    const uint32_t hp = hg ^ (1u << (b - L));
-    // intermediate outputs (bsel >= 3) live only in this context, unsharded
-    const double2* src = bsel < 3 ? tile_ptr(P, bsel, hp)
-                                  : psi + ((size_t)(hp & ((1u << P.tbl) - 1u)) << L);
+    if ((V.hg >> (b - L)) & 1u) continue;  // uniform: this tile holds bit value 1, no X / Y terms
+    const double2* src = obs_partner_tile(V, V.hg ^ (1u << (b - L)));
     double ore = 0.0, oim = 0.0;
-    if (live) {
+    if (V.live) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const double2 s = src[r * NT + tid];
@@ -426,11 +391,11 @@ k_obs_sites(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
     const int b = i / 3, c = i - 3 * b;
     if (i == 3 * n || (b < n && b >= L && c == 2)) {
       for (int w = 0; w < NW; ++w) v += s_n2[w];
-      if (i != 3 * n) v *= ((hg >> (b - L)) & 1u) ? -0.5 : 0.5;
-    } else if (b < n && !(b >= L && ((hg >> (b - L)) & 1u))) {
+      if (i != 3 * n) v *= ((V.hg >> (b - L)) & 1u) ? -0.5 : 0.5;
+    } else if (b < n && !(b >= L && ((V.hg >> (b - L)) & 1u))) {
       for (int w = 0; w < NW; ++w) v += s_red[b][w][c];
     }
-    partial[i] = v;
+    V.partial[i] = v;
   }
 }
 
@@ -614,22 +579,6 @@ hipError_t launch_step_L(int mode, const DevProb* probs, const int2* items, int 
   return hipGetLastError();
 }
 
-template <int L>
-hipError_t launch_obs_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                        double* partial, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items, bsel,
-                     partial, out_stride, xq);
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_obs_sites_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                              double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs_sites<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
-                     bsel, partial, out_stride, xq, S);
-  return hipGetLastError();
-}
-
 // <a|b> pieces for dse_energy: per block sum Re(conj(a) b) and sum |a|^2 over a grid-stride
 // range (fixed grid, fixed order: bitwise deterministic).
 __global__ void __launch_bounds__(256)
@@ -643,11 +592,7 @@ k_dot(const double2* __restrict__ a, const double2* __restrict__ b, size_t n, do
     e += x.x * y.x + x.y * y.y;
     q += x.x * x.x + x.y * x.y;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    e += __shfl_xor(e, off, 64);
-    q += __shfl_xor(q, off, 64);
-  }
+  wave_sum(e, q);
   if ((threadIdx.x & 63) == 0) {
     s_red[threadIdx.x >> 6][0] = e;
     s_red[threadIdx.x >> 6][1] = q;
@@ -661,44 +606,32 @@ k_dot(const double2* __restrict__ a, const double2* __restrict__ b, size_t n, do
 
 }  // namespace
 
-#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
-
 hipError_t launch_step(int L, int mode, const DevProb* probs, const int2* items, int n_items,
                        int k, int q, int set, hipStream_t st) {
   if (n_items <= 0) return hipSuccess;
-  switch (L) {
-#define X(l) \
-  case l: return launch_step_L<l>(mode, probs, items, n_items, k, q, set, st);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) { return launch_step_L<l()>(mode, probs, items, n_items, k, q, set, st); });
 }
 
 hipError_t launch_obs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                       double* partial, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if (n_out > 1 && bsel >= 3) return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_L<l>(probs, items, n_items, bsel, partial, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel, partial,
+                       out_stride, xq);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_obs_sites(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                             double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if ((n_out > 1 && bsel >= 3) || S < 2) return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_sites_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs_sites<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel,
+                       partial, out_stride, xq, S);
+    return hipGetLastError();
+  });
 }
 
 // one basis state per register: grid.y = entry, grid-stride over its amplitudes (16-B stores)

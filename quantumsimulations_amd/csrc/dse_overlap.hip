@@ -9,7 +9,7 @@
 // and zero elsewhere up to S.  Unlike every other observable of the engine the sum is not invariant
 // under psi -> e^{i theta} psi: it carries the phase of the state the engine defines.
 //
-//   k_obs_overlap<L>    tiled registers: k_obs_sites' arguments and addressing
+//   k_obs_overlap<L>    tiled registers: arguments and addressing are ObsTile's (dse_device.h)
 // (the dense engine's columns: k_dense_obs_overlap, dse_dense.hip, beside the phases it restores;
 // the small engine: small_overlap_sums, dse_small.hip)
 #include "dse_device.h"
@@ -29,55 +29,42 @@ __global__ void __launch_bounds__(Geo<L>::NT)
 k_obs_overlap(const DevProb* __restrict__ probs, const int2* __restrict__ items, int bsel_last,
               double* __restrict__ partial, size_t out_stride, int xq, int S) {
   using G = Geo<L>;
-  constexpr int T = G::T, NT = G::NT, R = G::R, NW = NT / 64;
+  constexpr int NT = G::NT, R = G::R, NW = NT / 64;
   __shared__ double s_red[2 * kMaxOverlapRefs + 1][NW];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, S);
+  const DevProb& P = V.P;
   const int K = P.ovl_k;
   if (K <= 0) return;
-  const uint32_t h = (uint32_t)it.y;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const bool lane0 = (tid & 63) == 0;
-  const bool live = (T >= NT) || (tid < T);
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
-  const gd2* gpsi = gptr(psi + base);
+  const int tid = V.tid;
+  const gd2* gpsi = gptr(V.psi + V.base);
 
   double2 own[R];
   double n2 = 0.0;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    own[r] = live ? gld(gpsi, r * NT + tid) : make_double2(0.0, 0.0);
+    own[r] = V.live ? gld(gpsi, r * NT + tid) : make_double2(0.0, 0.0);
     n2 += own[r].x * own[r].x + own[r].y * own[r].y;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
-  if (lane0) s_red[2 * kMaxOverlapRefs][wv] = n2;
+  wave_sum(n2);
+  if (V.lane0) s_red[2 * kMaxOverlapRefs][V.wv] = n2;
 
 #pragma unroll 1
   for (int k = 0; k < K; ++k) {
-    const gd2* gref = gptr(P.ovl_refs[k] + base);
+    const gd2* gref = gptr(P.ovl_refs[k] + V.base);
     double2 f[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) f[r] = live ? gld(gref, r * NT + tid) : make_double2(0.0, 0.0);
+    for (int r = 0; r < R; ++r) f[r] = V.live ? gld(gref, r * NT + tid) : make_double2(0.0, 0.0);
     double re = 0.0, im = 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {  // conj(phi) psi
       re += f[r].x * own[r].x + f[r].y * own[r].y;
       im += f[r].x * own[r].y - f[r].y * own[r].x;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      re += __shfl_xor(re, off, 64);
-      im += __shfl_xor(im, off, 64);
-    }
-    if (lane0) {
-      s_red[2 * k][wv] = re;
-      s_red[2 * k + 1][wv] = im;
+    wave_sum(re, im);
+    if (V.lane0) {
+      s_red[2 * k][V.wv] = re;
+      s_red[2 * k + 1][V.wv] = im;
     }
   }
   __syncthreads();
@@ -86,33 +73,21 @@ k_obs_overlap(const DevProb* __restrict__ probs, const int2* __restrict__ items,
     double v = 0.0;
     if (src >= 0)
       for (int w = 0; w < NW; ++w) v += s_red[src][w];
-    partial[i] = v;
+    V.partial[i] = v;
   }
 }
 
-template <int L>
-hipError_t launch_obs_overlap_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                                double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs_overlap<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
-                     bsel, partial, out_stride, xq, S);
-  return hipGetLastError();
-}
-
 }  // namespace
-
-#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
 
 hipError_t launch_obs_overlap(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                               double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if ((n_out > 1 && bsel >= 3) || S < 4 || S > overlap_stride(kMaxOverlapRefs)) return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_overlap_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs_overlap<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel,
+                       partial, out_stride, xq, S);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace dse

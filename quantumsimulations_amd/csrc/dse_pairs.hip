@@ -9,7 +9,7 @@
 // amplitude pair {x, y} is visited once, from the side with bit_i(x) = 0; bit_j(x) then says
 // whether the product belongs to ZQ or DQ, so one partner read serves both.
 //
-//   k_obs_pairs<L>      tiled registers: k_obs_sites' arguments and addressing
+//   k_obs_pairs<L>      tiled registers: arguments and addressing are ObsTile's (dse_device.h)
 //   k_dense_obs_pairs   the dense engine's columns, the non-uniform FFT's blocks, matrix mode's states
 #include "dse_dense.h"
 #include "dse_device.h"
@@ -22,7 +22,7 @@ constexpr int kPairBatch = 32;
 
 // Per tile the S >= pair_stride(n_max) partial sums of the layout above.  The three routes to the
 // partner amplitude are k_obs_sites' (register bit: another row of this thread; thread bit: LDS;
-// bit >= L: the partner tile through tile_ptr):
+// bit >= L: the partner tile, obs_partner_tile):
 //   i, j register bits   row r ^ e_i ^ e_j, chosen at compile time (the j and i loops unroll)
 //   i or j a thread bit  LDS at idx ^ e_i ^ e_j
 //   j >= L > i           tile hg ^ e_j, element idx ^ e_i
@@ -43,18 +43,9 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
   __shared__ double s_n2[NW];
   __shared__ int s_pair[kPairBatch];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
-  const uint32_t h = (uint32_t)it.y;
-  const uint32_t hg = P.h_base | h;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const bool lane0 = (tid & 63) == 0;
-  const bool live = (T >= NT) || (tid < T);
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, S);
+  const DevProb& P = V.P;
+  const int tid = V.tid;
   const int n = P.n;
   const int np = n * (n - 1) / 2;
 
@@ -64,8 +55,8 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     own[r] = make_double2(0.0, 0.0);
-    if (live) {
-      own[r] = psi[base + r * NT + tid];
+    if (V.live) {
+      own[r] = V.psi[V.base + r * NT + tid];
       s_w[r * NT + tid] = own[r];
     }
     p2[r] = own[r].x * own[r].x + own[r].y * own[r].y;
@@ -74,9 +65,8 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
   __syncthreads();
   {
     double v = p2sum;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane0) s_n2[wv] = v;
+    wave_sum(v);
+    if (V.lane0) s_n2[V.wv] = v;
   }
 
   int slot = 0;  // pairs waiting in s_red (uniform)
@@ -86,7 +76,7 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
       const int s = i / 5, c = i - 5 * s;
       double v = 0.0;
       for (int w = 0; w < NW; ++w) v += s_red[s][w][c];
-      partial[5 * s_pair[s] + c] = v;
+      V.partial[5 * s_pair[s] + c] = v;
     }
     __syncthreads();
     slot = 0;
@@ -95,12 +85,10 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
   auto wave_put = [&](int p, double zz, double qr, double qi, double dr, double di) {
     double v[5] = {zz, qr, qi, dr, di};
 #pragma unroll
-    for (int k = 0; k < 5; ++k)
+    for (int k = 0; k < 5; ++k) wave_sum(v[k]);
+    if (V.lane0)
 #pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
-    if (lane0)
-#pragma unroll
-      for (int k = 0; k < 5; ++k) s_red[slot][wv][k] = v[k];
+      for (int k = 0; k < 5; ++k) s_red[slot][V.wv][k] = v[k];
     if (tid == 0) s_pair[slot] = p;
     if (++slot == kPairBatch) flush();
   };
@@ -138,7 +126,7 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
         const uint32_t idx = (uint32_t)(r * NT + tid);
         const bool j1 = (idx >> j) & 1u;
         zz += (i1 != j1 ? -0.25 : 0.25) * p2[r];
-        if (i1 || !live) continue;
+        if (i1 || !V.live) continue;
         const double2 s = s_w[idx ^ m];
         const double re = own[r].x * s.x + own[r].y * s.y, im = own[r].x * s.y - own[r].y * s.x;
         qr += j1 ? re : 0.0;
@@ -150,31 +138,28 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
     }
   }
   // j above the tile: bit_j is the tile's
-  const uint32_t tmask = (1u << P.tbl) - 1u;
   for (int j = L; j < n; ++j) {
-    const bool j1 = (hg >> (j - L)) & 1u;
-    const uint32_t hj = hg ^ (1u << (j - L));
+    const bool j1 = (V.hg >> (j - L)) & 1u;
+    const uint32_t hj = V.hg ^ (1u << (j - L));
     for (int i = 0; i < j; ++i) {
       double zz = 0.0, ar = 0.0, ai = 0.0;
       if (i < L) {  // element idx ^ e_i of the tile hg ^ e_j
-        // intermediate outputs (bsel >= 3) live only in this context, unsharded
-        const double2* src = bsel < 3 ? tile_ptr(P, bsel, hj) : psi + ((size_t)(hj & tmask) << L);
+        const double2* src = obs_partner_tile(V, hj);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const uint32_t idx = (uint32_t)(r * NT + tid);
           const bool i1 = (idx >> i) & 1u;
           zz += (i1 != j1 ? -0.25 : 0.25) * p2[r];
-          if (i1 || !live) continue;
+          if (i1 || !V.live) continue;
           const double2 s = src[idx ^ (1u << i)];
           ar += own[r].x * s.x + own[r].y * s.y;
           ai += own[r].x * s.y - own[r].y * s.x;
         }
       } else {  // the same element of the tile hg ^ e_i ^ e_j
-        const bool i1 = (hg >> (i - L)) & 1u;
+        const bool i1 = (V.hg >> (i - L)) & 1u;
         zz = (i1 != j1 ? -0.25 : 0.25) * p2sum;
-        if (!i1 && live) {  // (i1 uniform: the tiles holding bit_i = 1 read nothing)
-          const uint32_t hp = hj ^ (1u << (i - L));
-          const double2* src = bsel < 3 ? tile_ptr(P, bsel, hp) : psi + ((size_t)(hp & tmask) << L);
+        if (!i1 && V.live) {  // (i1 uniform: the tiles holding bit_i = 1 read nothing)
+          const double2* src = obs_partner_tile(V, hj ^ (1u << (i - L)));
 #pragma unroll
           for (int r = 0; r < R; ++r) {
             const double2 s = src[r * NT + tid];
@@ -191,20 +176,12 @@ k_obs_pairs(const DevProb* __restrict__ probs, const int2* __restrict__ items, i
     double v = 0.0;
     if (i == 5 * np)
       for (int w = 0; w < NW; ++w) v += s_n2[w];
-    partial[i] = v;
+    V.partial[i] = v;
   }
 }
 
-template <int L>
-hipError_t launch_obs_pairs_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                              double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs_pairs<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
-                     bsel, partial, out_stride, xq, S);
-  return hipGetLastError();
-}
-
-// Pair sums of the dense engine's columns (option pair_obs; layout parameters as k_dense_obs and
-// k_dense_obs_sites): P.pairs row t0 + j holds the record above, S doubles per row.  In the rotated
+// Pair sums of the dense engine's columns (option pair_obs; the columns' layout: DenseCols,
+// dse_dense.h): P.pairs row t0 + j holds the record above, S doubles per row.  In the rotated
 // frame (psi' = i^|x| psi) ZZ and ZQ are unchanged and DQ takes the factor -1: flipping two equal
 // bits changes the popcount by 2.  One pass over the column per pair (the column stays in L2), its
 // five sums reduced over the wave, then the four waves in order: no atomics.
@@ -214,8 +191,7 @@ k_dense_obs_pairs(const DenseProb* __restrict__ probs, int dim, const double* __
   __shared__ double red[4][5];
   const DenseProb& P = probs[blockIdx.y];
   const int jcol = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)jcol * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, jcol);
   const int n = P.n;
   const int np = n * (n - 1) / 2;
   double* o = P.pairs + (size_t)(t0 + jcol) * S;
@@ -244,9 +220,7 @@ k_dense_obs_pairs(const DenseProb* __restrict__ probs, int dim, const double* __
         v[3] += dq_sign * zr, v[4] += dq_sign * zi;
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    for (int k = 0; k < 5; ++k) wave_sum(v[k]);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
       for (int k = 0; k < 5; ++k) red[w][k] = v[k];
@@ -266,33 +240,21 @@ k_dense_obs_pairs(const DenseProb* __restrict__ probs, int dim, const double* __
 
 }  // namespace
 
-#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
-
 hipError_t launch_obs_pairs(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                             double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if ((n_out > 1 && bsel >= 3) || S < 2) return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_pairs_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs_pairs<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel,
+                       partial, out_stride, xq, S);
+    return hipGetLastError();
+  });
 }
 
-hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                  int tb, int t0, int S, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_pairs, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0, S);
-  return hipGetLastError();
-}
-
-// interleaved complex columns, one problem: the non-uniform FFT's blocks and matrix mode's states
-hipError_t launch_dense_obs_pairs_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                    hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_pairs, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0, S);
+hipError_t launch_dense_obs_pairs(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                  int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_pairs, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride,
+                     cols.colstride, cols.imoff, cols.es, t0, S);
   return hipGetLastError();
 }
 

@@ -2031,19 +2031,33 @@ void dense_worker(dse_ctx* ctx, const DenseRun& R, DenseRound& Rd, int w) {
   Rd.qcv.notify_one();
 }
 
+// The aggregates, then every family the context records (kObsLaunchOrder), of the tb columns `cols` of
+// the n-qubit registers d[0 .. count) into rows t0 .. t0 + tb of their records: the dense engine's
+// blocks on both paths and matrix mode's states.  A family is launched iff the context records it
+// (fam[f].on), and that is when d[p].*dense_out is set: dense_alloc_job gives a job the buffer of every
+// family that is on or fails, matrix_run does the same in its arena; the site and pair kernels write
+// through that pointer unchecked.
+hipError_t launch_dense_outputs(const dse_ctx* ctx, const DenseProb* d, int count, int n, const DenseCols& cols, int tb,
+                                int t0, hipStream_t st) {
+  const int dim = 1 << n;
+  hipError_t e = launch_dense_obs(d, count, dim, cols, tb, t0, st);
+  for (ObsFamily f : kObsLaunchOrder)
+    if (e == hipSuccess && ctx->fam[f].on)
+      e = kObsFamilies[f].launch_dense(d, count, dim, cols, tb, t0, kObsFamilies[f].stride(ctx, n), st);
+  return e;
+}
+
 // Job J's outputs by the non-uniform FFT: per register, Psi' interleaved, the observables per block
 int dense_outputs_nufft(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
   const int n_t = R.n_t;
   const size_t dim = J.dim;
   hipStream_t st = R.st;
+  const DenseCols cols = DenseCols::interleaved(J.Psi, (int)dim);
   for (int i = 0; i < J.cnt; ++i) {
     const DenseProb* di = J.d_desc + i;
     auto per_block = [&](int tb0, int tb) -> int {
-      if (launch_dense_obs_c(di, (int)dim, J.Psi, tb, tb0, st) != hipSuccess) return -1;
-      for (ObsFamily f : kObsLaunchOrder)
-        if (J.fam[f] && kObsFamilies[f].launch_dense_c(di, (int)dim, J.Psi, tb, tb0, kObsFamilies[f].stride(ctx, J.n), st) != hipSuccess)
-          return -1;
-      if (tb0 + tb == n_t && launch_dense_final_c(di, (int)dim, J.Psi, tb, R.tau[n_t - 1], st) != hipSuccess)
+      if (launch_dense_outputs(ctx, di, 1, J.n, cols, tb, tb0, st) != hipSuccess) return -1;
+      if (tb0 + tb == n_t && launch_dense_final(di, 1, (int)dim, cols, tb, R.tau[n_t - 1], st) != hipSuccess)
         return -1;
       return 0;
     };
@@ -2075,11 +2089,9 @@ int dense_outputs_gemm(dse_ctx* ctx, DenseRun& R, DenseJob& J) {
         J.Psi, (rocblas_int)dim, (rocblas_stride)pstride, cnt);
     if (rs != rocblas_status_success)
       return fail(ctx, DSE_ERR_HIP, "rocblas dgemm failed (status " + std::to_string((int)rs) + ")");
-    HIPC(launch_dense_obs(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, st));
-    for (ObsFamily f : kObsLaunchOrder)
-      if (J.fam[f])
-        HIPC(kObsFamilies[f].launch_dense(desc, cnt, (int)dim, J.Psi, pstride, tb, tb0, kObsFamilies[f].stride(ctx, J.n), st));
-    if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, J.Psi, pstride, tb, R.tau[n_t - 1], st));
+    const DenseCols cols = DenseCols::split(J.Psi, pstride, (int)dim, tb);
+    HIPC(launch_dense_outputs(ctx, desc, cnt, J.n, cols, tb, tb0, st));
+    if (tb0 + tb == n_t) HIPC(launch_dense_final(desc, cnt, (int)dim, cols, tb, R.tau[n_t - 1], st));
   }
   return DSE_OK;
 }
@@ -2429,13 +2441,13 @@ int matrix_run(dse_ctx* ctx, int pi, const double* t, int n_t, double dt, double
   D.sec_tab = P.d_sec_tab;
   D.sec_k = P.sec_k();
   HIPC(hipMemcpyAsync(d_desc, &D, sizeof(DenseProb), hipMemcpyHostToDevice, st));
-  HIPC(launch_state_obs(d_desc, (int)dim, S, n_t, 0, st));
+  const DenseCols cols = DenseCols::interleaved(reinterpret_cast<const double*>(S), (int)dim);
+  HIPC(launch_dense_outputs(ctx, d_desc, 1, n, cols, n_t, 0, st));
   std::vector<double> hfam[kNumObsFamilies];
   for (ObsFamily f : kObsLaunchOrder) {
     if (!ctx->fam[f].on) continue;
     const ObsFamilyDesc& F = kObsFamilies[f];
     hfam[f].resize((size_t)n_t * F.stride(ctx, n));
-    HIPC(F.launch_dense_c(d_desc, (int)dim, reinterpret_cast<const double*>(S), n_t, 0, F.stride(ctx, n), st));
     HIPC(hipMemcpyAsync(hfam[f].data(), D.*F.dense_out, hfam[f].size() * sizeof(double), hipMemcpyDeviceToHost, st));
   }
   HIPC(hipMemcpyAsync(P.buf[0], S + dim * (size_t)(n_t - 1), dim * sizeof(double2), hipMemcpyDeviceToDevice, st));

@@ -7,7 +7,7 @@
 // The record of a state: the bins of set k at [off_k + j], U = sum_k B_k in all, ||psi||^2 at
 // [S - 2], zero elsewhere up to S = sector_stride(U_max) of the context.
 //
-//   k_obs_sectors<L>      tiled registers: k_obs_strings' arguments and addressing
+//   k_obs_sectors<L>      tiled registers: arguments and addressing are ObsTile's (dse_device.h)
 //   k_dense_obs_sectors   the dense engine's columns, the non-uniform FFT's blocks, matrix mode's states
 // (the small engine: small_sector_sums, dse_small.hip)
 #include "dse_dense.h"
@@ -39,20 +39,11 @@ k_obs_sectors(const DevProb* __restrict__ probs, const int2* __restrict__ items,
   __shared__ double s_bin[kMaxSectorSets][NW][VL];
   __shared__ double s_nrm[NW];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, S);
+  const DevProb& P = V.P;
   const int K = P.sec_k;
   if (K <= 0) return;
-  const uint32_t h = (uint32_t)it.y;
-  const uint32_t hg = P.h_base | h;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const bool lane0 = (tid & 63) == 0;
-  const bool live = (T >= NT) || (tid < T);
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
+  const int tid = V.tid;
   const SectorEntry* __restrict__ tab = P.sec_tab;
 
   double p2[R];
@@ -60,29 +51,28 @@ k_obs_sectors(const DevProb* __restrict__ probs, const int2* __restrict__ items,
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     p2[r] = 0.0;
-    if (live) {
-      const double2 a = psi[base + r * NT + tid];
+    if (V.live) {
+      const double2 a = V.psi[V.base + r * NT + tid];
       p2[r] = a.x * a.x + a.y * a.y;
     }
     n2 += p2[r];
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
-  if (lane0) s_nrm[wv] = n2;
+  wave_sum(n2);
+  if (V.lane0) s_nrm[V.wv] = n2;
 
 #pragma unroll 1
   for (int k = 0; k < K; ++k) {
     const uint64_t m = tab[k].m, cm = tab[k].cm, cv = tab[k].cv;
-    if ((hg & (uint32_t)(cm >> L)) != (uint32_t)(cv >> L)) continue;  // (uniform: the tile's selecting bits)
+    if ((V.hg & (uint32_t)(cm >> L)) != (uint32_t)(cv >> L)) continue;  // (uniform: the tile's selecting bits)
     const uint32_t m_lo = (uint32_t)m & TM, cm_lo = (uint32_t)cm & TM, cv_lo = (uint32_t)cv & TM;
     double q[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) q[r] = (((uint32_t)(r * NT + tid)) & cm_lo) == cv_lo ? p2[r] : 0.0;
     double v[VL];
     sector_wave_bins<LR>(q, m_lo >> LGNT, m_lo & 63u, v);
-    if (lane0) {
+    if (V.lane0) {
 #pragma unroll
-      for (int c = 0; c < VL; ++c) s_bin[k][wv][c] = v[c];
+      for (int c = 0; c < VL; ++c) s_bin[k][V.wv][c] = v[c];
     }
   }
   __syncthreads();
@@ -93,9 +83,9 @@ k_obs_sectors(const DevProb* __restrict__ probs, const int2* __restrict__ items,
       int k = 0;
       while (k + 1 < K && i >= tab[k + 1].off) ++k;
       const uint64_t m = tab[k].m, cm = tab[k].cm, cv = tab[k].cv;
-      if ((hg & (uint32_t)(cm >> L)) == (uint32_t)(cv >> L)) {
+      if ((V.hg & (uint32_t)(cm >> L)) == (uint32_t)(cv >> L)) {
         const uint32_t m_wv = ((uint32_t)m & TM) >> 6;
-        const int c0 = i - tab[k].off - __popc(hg & (uint32_t)(m >> L));
+        const int c0 = i - tab[k].off - __popc(V.hg & (uint32_t)(m >> L));
         for (int w = 0; w < NW; ++w) {
           const int c = c0 - __popc((uint32_t)w & m_wv);
           if (c >= 0 && c < VL) v += s_bin[k][w][c];
@@ -104,19 +94,11 @@ k_obs_sectors(const DevProb* __restrict__ probs, const int2* __restrict__ items,
     } else if (i == S - 2) {
       for (int w = 0; w < NW; ++w) v += s_nrm[w];
     }
-    partial[i] = v;
+    V.partial[i] = v;
   }
 }
 
-template <int L>
-hipError_t launch_obs_sectors_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                                double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs_sectors<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
-                     bsel, partial, out_stride, xq, S);
-  return hipGetLastError();
-}
-
-// Sector populations of the dense engine's columns (layout parameters as k_dense_obs_strings, one
+// Sector populations of the dense engine's columns (the columns' layout: DenseCols, dse_dense.h; one
 // workgroup per column): P.secs row t0 + j holds the record above, S doubles per row.  The rotated
 // frame (P.rot: psi' = i^|x| psi) needs nothing here: |psi'_x| = |psi_x|, and the psi0 phase and the
 // shift's phase have modulus 1.  One pass over the column per set (the column stays in L2) and one
@@ -132,8 +114,7 @@ k_dense_obs_sectors(const DenseProb* __restrict__ probs, int dim, const double* 
   const int K = P.sec_k;
   if (K <= 0 || !P.secs) return;
   const int j = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, j);
   double* o = P.secs + (size_t)(t0 + j) * S;
   const int w = threadIdx.x >> 6;
   const int U = P.sec_tab[K - 1].off + P.sec_tab[K - 1].bins;
@@ -154,8 +135,7 @@ k_dense_obs_sectors(const DenseProb* __restrict__ probs, int dim, const double* 
     }
 #pragma unroll
     for (int c = 0; c < kDenseBins; ++c) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+      wave_sum(v[c]);
       if ((threadIdx.x & 63) == 0) red[w][c] = v[c];
     }
     __syncthreads();
@@ -171,36 +151,23 @@ k_dense_obs_sectors(const DenseProb* __restrict__ probs, int dim, const double* 
 
 }  // namespace
 
-#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
-
 hipError_t launch_obs_sectors(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                               double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if ((n_out > 1 && bsel >= 3) || S < 3 || S > sector_stride(kMaxSectorSets * (kMaxQubits + 1)))
     return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_sectors_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs_sectors<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel,
+                       partial, out_stride, xq, S);
+    return hipGetLastError();
+  });
 }
 
-hipError_t launch_dense_obs_sectors(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st) {
+hipError_t launch_dense_obs_sectors(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st) {
   if (dim > (1 << kDenseMaxQubits)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_dense_obs_sectors, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0, S);
-  return hipGetLastError();
-}
-
-// interleaved complex columns, one problem: the non-uniform FFT's blocks and matrix mode's states
-hipError_t launch_dense_obs_sectors_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st) {
-  if (dim > (1 << kDenseMaxQubits)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_dense_obs_sectors, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0, S);
+  hipLaunchKernelGGL(k_dense_obs_sectors, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride,
+                     cols.colstride, cols.imoff, cols.es, t0, S);
   return hipGetLastError();
 }
 

@@ -9,7 +9,7 @@
 // The record of a state: Re, Im of S_k at [2 k], [2 k + 1] for k < K, ||psi||^2 at [S - 2], zero
 // elsewhere up to S = string_stride(K_max) of the context.
 //
-//   k_obs_strings<L>      tiled registers: k_obs_pairs' arguments and addressing
+//   k_obs_strings<L>      tiled registers: arguments and addressing are ObsTile's (dse_device.h)
 //   k_dense_obs_strings   the dense engine's columns, the non-uniform FFT's blocks, matrix mode's states
 // (the small engine: small_string_sums, dse_small.hip)
 #include "dse_dense.h"
@@ -24,7 +24,7 @@ namespace {
 //   xm == 0           no partner: signed, selected |psi|^2
 //   xm >> L == 0      LDS at idx ^ xm_lo (thread and row bits alike: nothing indexed by the string
 //                     sits in a per-thread array)
-//   xm >> L != 0      tile hg ^ xm_hi through tile_ptr, element idx ^ xm_lo: a xor of lane indices
+//   xm >> L != 0      tile hg ^ xm_hi (obs_partner_tile), element idx ^ xm_lo: a xor of lane indices
 //                     permutes within aligned runs, so the loads stay coalesced
 // Selected and signing bits at or above L are the tile's own: a tile that fails the selection reads
 // nothing and contributes zeros; the tile's sign multiplies the finished sums.  Each string's two
@@ -42,21 +42,11 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
   __shared__ double2 s_w[T];
   __shared__ double s_red[2 * kMaxOpStrings + 1][NW];
 
-  const int2 it = items[blockIdx.x];
-  const DevProb& P = probs[it.x];
+  const ObsTile<L> V = obs_tile<L>(probs, items, bsel_last, partial, out_stride, xq, S);
+  const DevProb& P = V.P;
   const int K = P.str_k;
   if (K <= 0) return;
-  const uint32_t h = (uint32_t)it.y;
-  const uint32_t hg = P.h_base | h;
-  const int tid = threadIdx.x;
-  const int wv = tid >> 6;
-  const bool lane0 = (tid & 63) == 0;
-  const bool live = (T >= NT) || (tid < T);
-  const int bsel = (blockIdx.y == gridDim.y - 1) ? bsel_last : 3 + (int)blockIdx.y;
-  partial += (size_t)blockIdx.y * out_stride + (size_t)blockIdx.x * S;
-  const double2* psi = bsel < 3 ? P.buf[bsel] : P.xacc + ((size_t)(xq * P.xacc_q + bsel - 3) << (L + P.tbl));
-  const size_t base = (size_t)h << L;
-  const uint32_t tmask = (1u << P.tbl) - 1u;
+  const int tid = V.tid;
   const StringEntry* __restrict__ tab = P.str_tab;
 
   double2 own[R];
@@ -65,17 +55,16 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     own[r] = make_double2(0.0, 0.0);
-    if (live) {
-      own[r] = psi[base + r * NT + tid];
+    if (V.live) {
+      own[r] = V.psi[V.base + r * NT + tid];
       s_w[r * NT + tid] = own[r];
     }
     p2[r] = own[r].x * own[r].x + own[r].y * own[r].y;
     n2 += p2[r];
   }
   __syncthreads();
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) n2 += __shfl_xor(n2, off, 64);
-  if (lane0) s_red[2 * kMaxOpStrings][wv] = n2;
+  wave_sum(n2);
+  if (V.lane0) s_red[2 * kMaxOpStrings][V.wv] = n2;
 
 #pragma unroll 1
   for (int k = 0; k < K; ++k) {
@@ -83,7 +72,7 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
     const uint32_t xm_lo = (uint32_t)xm & TM, xm_hi = (uint32_t)(xm >> L);
     const uint32_t zm_lo = (uint32_t)zm & TM, cm_lo = (uint32_t)cm & TM, cv_lo = (uint32_t)cv & TM;
     double re = 0.0, im = 0.0;
-    if ((hg & (uint32_t)(cm >> L)) == (uint32_t)(cv >> L)) {  // (uniform: the tile's selected bits)
+    if ((V.hg & (uint32_t)(cm >> L)) == (uint32_t)(cv >> L)) {  // (uniform: the tile's selected bits)
       if (xm == 0) {
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -91,12 +80,8 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
           const double q = (idx & cm_lo) == cv_lo ? p2[r] : 0.0;
           re += par32(idx & zm_lo) ? -q : q;
         }
-      } else if (live) {
-        const double2* src = s_w;
-        if (xm_hi) {  // intermediate outputs (bsel >= 3) live only in this context, unsharded
-          const uint32_t hp = hg ^ xm_hi;
-          src = bsel < 3 ? tile_ptr(P, bsel, hp) : psi + ((size_t)(hp & tmask) << L);
-        }
+      } else if (V.live) {
+        const double2* src = xm_hi ? obs_partner_tile(V, V.hg ^ xm_hi) : s_w;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
           const uint32_t idx = (uint32_t)(r * NT + tid);
@@ -108,16 +93,12 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
           im += neg ? -zi : zi;
         }
       }
-      if (par32(hg & (uint32_t)(zm >> L))) re = -re, im = -im;
+      if (par32(V.hg & (uint32_t)(zm >> L))) re = -re, im = -im;
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      re += __shfl_xor(re, off, 64);
-      im += __shfl_xor(im, off, 64);
-    }
-    if (lane0) {
-      s_red[2 * k][wv] = re;
-      s_red[2 * k + 1][wv] = im;
+    wave_sum(re, im);
+    if (V.lane0) {
+      s_red[2 * k][V.wv] = re;
+      s_red[2 * k + 1][V.wv] = im;
     }
   }
   __syncthreads();
@@ -132,19 +113,11 @@ k_obs_strings(const DevProb* __restrict__ probs, const int2* __restrict__ items,
     } else if (i == S - 2) {
       for (int w = 0; w < NW; ++w) v += s_red[2 * kMaxOpStrings][w];
     }
-    partial[i] = v;
+    V.partial[i] = v;
   }
 }
 
-template <int L>
-hipError_t launch_obs_strings_L(const DevProb* probs, const int2* items, int n_items, int bsel,
-                                double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
-  hipLaunchKernelGGL((k_obs_strings<L>), dim3(n_items, n_out), dim3(Geo<L>::NT), 0, st, probs, items,
-                     bsel, partial, out_stride, xq, S);
-  return hipGetLastError();
-}
-
-// Operator strings of the dense engine's columns (layout parameters as k_dense_obs_pairs, one
+// Operator strings of the dense engine's columns (the columns' layout: DenseCols, dse_dense.h; one
 // workgroup per column): P.strs row t0 + j holds the record above, S doubles per row.  In the rotated
 // frame (P.rot: psi' = i^|x| psi) conj(psi_x) psi_{x ^ xm} = (-i)^|xm| (-1)^|x & xm| conj(psi'_x)
 // psi'_{x ^ xm}, so the same sum holds with zm' = zm ^ xm and pre' = pre (-i)^popcount(xm) (I+ I+:
@@ -159,8 +132,7 @@ k_dense_obs_strings(const DenseProb* __restrict__ probs, int dim, const double* 
   const int K = P.str_k;
   if (K <= 0 || !P.strs) return;
   const int j = blockIdx.x;
-  const double* re = Psi + blockIdx.y * pstride + (size_t)j * colstride;
-  const double* im = re + imoff;
+  const auto [re, im] = dense_col(Psi, pstride, colstride, imoff, blockIdx.y, j);
   double* o = P.strs + (size_t)(t0 + j) * S;
   const int w = threadIdx.x >> 6;
   for (int k = 0; k <= K; ++k) {  // k == K: the norm alone
@@ -183,9 +155,7 @@ k_dense_obs_strings(const DenseProb* __restrict__ probs, int dim, const double* 
       v[1] += neg ? -zi : zi;
     }
 #pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off, 64);
+    for (int c = 0; c < 2; ++c) wave_sum(v[c]);
     if ((threadIdx.x & 63) == 0) red[w][0] = v[0], red[w][1] = v[1];
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -212,33 +182,21 @@ k_dense_obs_strings(const DenseProb* __restrict__ probs, int dim, const double* 
 
 }  // namespace
 
-#define DSE_TILE_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
-
 hipError_t launch_obs_strings(int L, const DevProb* probs, const int2* items, int n_items, int bsel,
                               double* partial, int S, hipStream_t st, int n_out, size_t out_stride, int xq) {
   if (n_items <= 0 || n_out <= 0) return hipSuccess;
   if ((n_out > 1 && bsel >= 3) || S < 4 || S > string_stride(kMaxOpStrings)) return hipErrorInvalidValue;
-  switch (L) {
-#define X(l) \
-  case l: return launch_obs_strings_L<l>(probs, items, n_items, bsel, partial, S, st, n_out, out_stride, xq);
-    DSE_TILE_CASES(X)
-#undef X
-    default: return hipErrorInvalidValue;
-  }
+  return for_tile_bits(L, [&](auto l) {
+    hipLaunchKernelGGL((k_obs_strings<l()>), dim3(n_items, n_out), dim3(Geo<l()>::NT), 0, st, probs, items, bsel,
+                       partial, out_stride, xq, S);
+    return hipGetLastError();
+  });
 }
 
-hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const double* Psi, size_t pstride,
-                                    int tb, int t0, int S, hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_strings, dim3(tb, count), dim3(256), 0, st, d, dim, Psi, pstride, (size_t)dim,
-                     (size_t)tb * dim, 1, t0, S);
-  return hipGetLastError();
-}
-
-// interleaved complex columns, one problem: the non-uniform FFT's blocks and matrix mode's states
-hipError_t launch_dense_obs_strings_c(const DenseProb* d, int dim, const double* Psi, int tb, int t0, int S,
-                                      hipStream_t st) {
-  hipLaunchKernelGGL(k_dense_obs_strings, dim3(tb, 1), dim3(256), 0, st, d, dim, Psi, (size_t)0, (size_t)2 * dim,
-                     (size_t)1, 2, t0, S);
+hipError_t launch_dense_obs_strings(const DenseProb* d, int count, int dim, const DenseCols& cols, int tb, int t0,
+                                    int S, hipStream_t st) {
+  hipLaunchKernelGGL(k_dense_obs_strings, dim3(tb, count), dim3(256), 0, st, d, dim, cols.Psi, cols.pstride,
+                     cols.colstride, cols.imoff, cols.es, t0, S);
   return hipGetLastError();
 }
 
